@@ -12,13 +12,19 @@ output a PyMARL runner consumes written to HBM (positions, dones, t, reward,
 term, node/edge collisions, avail mask, window obs).  The timed path is the
 fused rollout kernel (`mapfx_rollout`, T steps per launch, state kept on
 chip); the per-step drop-in path (`mapfx_step`, one launch per step, state
-round-trips HBM) is measured too and reported under "per_step".
+round-trips HBM) is measured too under --full and reported under "per_step".
 
 The timed K env steps run as launches of T = min(K, --chunk) fused steps (one
 launch of T = 20 at the driver's --steps 20), every launch prepared before the
 timed region so it holds only the foreign calls.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run sets up, warms up, times the K steps and prints the result line.
+--full adds every other measurement to the line: the event-timed kernel replays and
+the roofline they feed, the per-step path, the CPU baselines and the PMC profile's
+traffic.  --dump-outputs DIR writes what the last timed step computed, one
+DIR/<name>.npy per output, for comparing two builds output for output.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
        python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 With --gpus N > 1 and no torchrun environment, bench.py starts the N rank
 processes itself (launch_ranks) and refuses to run when fewer than N HIP devices
@@ -59,9 +65,16 @@ def parse():
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     ap.add_argument("--chunk", type=int, default=64, help="env steps per rollout launch")
     ap.add_argument("--window", type=int, default=5)
-    ap.add_argument("--per-step-steps", type=int, default=200)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: event-timed "
+                         "kernel replays + roofline, the per-step path, the CPU baseline, the "
+                         "PMC profile's traffic")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed env step as DIR/<name>.npy")
+    ap.add_argument("--per-step-steps", type=int, default=200,
+                    help="--full: launches of the per-step leg (0 disables)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0,
-                    help="target CPU work of the cpu_baseline sample (0 disables)")
+                    help="--full: target CPU work of the cpu_baseline sample (0 disables)")
     ap.add_argument("--no-gather", action="store_true",
                     help="N > 1: skip the RCCL gather leg (reported beside the compute-only value)")
     ap.add_argument("--gather-payload", default="compact",
@@ -123,6 +136,34 @@ def bench_traj(b, T):
     traj = b._alloc_out(T)
     traj.pop("reward_f32")
     return traj
+
+
+DUMP_BUDGET = 48 << 20     # bytes of all dumped arrays together (the limit is 64 MB)
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array of `arrays` (name -> tensor or ndarray) as
+    DIR/<name>.npy, float64 for 8-byte elements and float32 for everything else
+    (integers up to 2^24 are exact in it).  Arrays that together would exceed
+    DUMP_BUDGET are cut, largest first, to a fixed seeded sample of their elements
+    (the same indices in every run of the same arguments), saved flat."""
+    os.makedirs(dirname, exist_ok=True)
+    host = {}
+    for k, v in arrays.items():
+        a = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        host[k] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype.itemsize == 8 else np.float32)
+    over = sum(a.nbytes for a in host.values()) - DUMP_BUDGET
+    for k in sorted(host, key=lambda k: -host[k].nbytes):
+        if over <= 0:
+            break
+        a = host[k]
+        keep = max(1, (a.nbytes - over) // a.itemsize, (1 << 20) // a.itemsize)
+        if keep < a.size:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            host[k] = a.reshape(-1)[idx]
+            over -= a.nbytes - host[k].nbytes
+    for k, a in host.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
 
 
 def out_bytes_per_env_step(N, W):
@@ -302,7 +343,8 @@ def main():
     # (KREP passes of the K steps, at least 15 launches in all; the median pass is
     # reported, so one disturbed launch does not move the roofline, and a rocprofv3 trace
     # of the command averages enough launches to compare with it)
-    KREP = max(5, -(-15 // nl))
+    # (--full only: a plain run neither creates the events nor replays anything)
+    KREP = max(5, -(-15 // nl)) if args.full else 0
     evs = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             for _ in range(nl)] for _ in range(KREP)]
     for rep_evs in evs:     # torch creates the HIP events at their first record()
@@ -319,7 +361,7 @@ def main():
     # then run the timed launches' exact work (a state hundreds of steps further on is a
     # different workload -- C3's done agents crowd the aisles: 175 -> 223 us per launch,
     # profiles/r05_c3_trace_gaps.json)
-    state0 = [x.clone() for x in (b.pos, b.done, b.t)]
+    state0 = [x.clone() for x in (b.pos, b.done, b.t)] if args.full else []
     if dist:
         dist.barrier()
     torch.cuda.synchronize()
@@ -335,6 +377,10 @@ def main():
     if dist:
         dist.barrier()
     torch.cuda.synchronize()
+    if args.dump_outputs and rank == 0:
+        # the last timed launch's buffers, before anything else touches them
+        t_last = rem or T
+        dump_outputs(args.dump_outputs, {k: v[t_last - 1] for k, v in traj.items()})
     for kp in kplans:       # kernel timing passes (untimed wall clock)
         for x, x0 in zip((b.pos, b.done, b.t), state0):
             x.copy_(x0)
@@ -342,8 +388,10 @@ def main():
             pl()
     torch.cuda.synchronize()
     kern_passes = sorted(sum(a_.elapsed_time(b_) for a_, b_ in rep_evs) for rep_evs in evs)
-    kern_ms_total = kern_passes[KREP // 2]     # median pass; events on the launch stream
-    kern_ms = kern_ms_total / len(plans)
+    kern_ms_total = kern_ms = None
+    if args.full:
+        kern_ms_total = kern_passes[KREP // 2]     # median pass; events on the launch stream
+        kern_ms = kern_ms_total / len(plans)
     el = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
     if dist:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
@@ -356,14 +404,14 @@ def main():
                     + (8 + 1) * N + 4)             # per-launch state read + write-back
     timed_bytes = E * K * bpes + len(plans) * state_io
     launch_bytes = timed_bytes / len(plans)
-    achieved = timed_bytes / (kern_ms_total * 1e-3) / 1e9
+    achieved = timed_bytes / (kern_ms_total * 1e-3) / 1e9 if args.full else None
 
     # ---- per-step path (one mapfx_step launch per env step) ----
     # `ks` launches captured once as a HIP graph and replayed: kernels back to back,
     # no Python / ctypes launch overhead between them ("eager" = one Python call
     # per step, as the drop-in env does it, reported beside it).
     per_step = None
-    if args.per_step_steps > 0:
+    if args.full and args.per_step_steps > 0:
         b2 = mapfx.MapfGridBatch(inst["init_pos"], inst["goals"], bits=inst["bits"], hw=(S, S),
                                  episode_limit=limit, obs=(wkind,), window=W,
                                  device="cuda:%d" % local, env_offset=offset, track_steps=False)
@@ -440,11 +488,8 @@ def main():
 
     # ---- CPU baseline: the oracle's C restatement on this host (rank 0, N=1) ----
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         cpu = cpu_baseline(inst, S, N, E, W, args.cpu_seconds)
-
-    traffic, traffic_src = profile_traffic(args.config, kernel=kernel_name, path=args.pmc,
-                                           config=args.config, T=T, E=E)
 
     if rank == 0:
         line = {
@@ -454,7 +499,7 @@ def main():
             "n_gpus": world,
             "steps": K,
             "warmup": WU,
-            "ms_per_step": round(elapsed / K * 1e3, 5),
+            "ms_per_step": round(elapsed / K * 1e3, 7),    # a step is ~1 us: 3+ digits of it
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -474,25 +519,31 @@ def main():
                        + (" (REHEARSAL: all ranks on cuda:0 over gloo)" if args.rehearse_shared_gpu
                           else "")},
             "env_steps_per_s": round(total_envs * K / elapsed, 1),
-            "kernel_ms_per_launch": round(kern_ms, 5),
             "kernel": kernel_name,
             "build_id": _abi.build_id(),
-            "timing": {"wall_ms": round(elapsed * 1e3, 4),
-                       "kernel_ms_events": round(kern_ms_total, 4),
-                       "kernel_timing": "per-launch start/stop events recorded at the "
-                                        "kernel's begin/end (hipExtLaunchKernel) on %d replays "
-                                        "of the same launches right after the timed region; "
-                                        "median replay" % KREP,
-                       "kernel_ms_replays": [round(x, 4) for x in kern_passes],
-                       "launches": len(plans),
-                       "wall_over_kernel": round(elapsed * 1e3 / kern_ms_total, 3)},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "bytes_per_env_step": bpes, "bytes_per_launch": int(launch_bytes)},
-            "per_step": per_step,
-            "cpu_baseline": cpu,
+            "timing": {"wall_ms": round(elapsed * 1e3, 4), "launches": len(plans)},
         }
+        if args.full:
+            traffic, traffic_src = profile_traffic(args.config, kernel=kernel_name, path=args.pmc,
+                                                   config=args.config, T=T, E=E)
+            line.update({
+                "kernel_ms_per_launch": round(kern_ms, 5),
+                "timing": {"wall_ms": round(elapsed * 1e3, 4),
+                           "kernel_ms_events": round(kern_ms_total, 4),
+                           "kernel_timing": "per-launch start/stop events recorded at the "
+                                            "kernel's begin/end (hipExtLaunchKernel) on %d replays "
+                                            "of the same launches right after the timed region; "
+                                            "median replay" % KREP,
+                           "kernel_ms_replays": [round(x, 4) for x in kern_passes],
+                           "launches": len(plans),
+                           "wall_over_kernel": round(elapsed * 1e3 / kern_ms_total, 3)},
+                "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+                             "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                             "traffic": traffic, "traffic_source": traffic_src,
+                             "bytes_per_env_step": bpes, "bytes_per_launch": int(launch_bytes)},
+                "per_step": per_step,
+                "cpu_baseline": cpu,
+            })
         if gather is not None:
             line["gather"] = gather
         print(json.dumps(line), flush=True)
@@ -727,14 +778,18 @@ def run_partial(args, dist, rank, world, local):
     if dist:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     elapsed = float(el.item())
+    if args.dump_outputs and rank == 0:     # what the episode's last step left
+        dump_outputs(args.dump_outputs, dict(b.out, pos=b.pos, terminated=b.terminated))
     # the drop-in style (one Python call per step) for reference
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    b.reset()
-    for k in range(limit):
-        b.step(acts[k])
-    torch.cuda.synchronize()
-    eager_ms = (time.perf_counter() - t1) / limit * 1e3
+    eager_ms = None
+    if args.full:
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        b.reset()
+        for k in range(limit):
+            b.step(acts[k])
+        torch.cuda.synchronize()
+        eager_ms = (time.perf_counter() - t1) / limit * 1e3
     from mapfx import _abi
     kernel_name = _abi.last_kernel()     # the step instance the graph replays
     D = b.obs_dim
@@ -743,7 +798,7 @@ def run_partial(args, dist, rank, world, local):
     # traffic per launch (one env step of E envs) from the PMC profile of this workload
     traffic, traffic_src = profile_traffic("partial", kernel=kernel_name, E=E, N=N, S=S)
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         cpu = partial_cpu_baseline(inst, S, N, args.cpu_seconds)
     if rank == 0:
         print(json.dumps({
@@ -760,7 +815,7 @@ def run_partial(args, dist, rank, world, local):
                        "parallelism": "env-shard x%d" % world},
             "env_steps_per_s": round(E * world * K / elapsed, 1),
             "kernel_ms_per_step": round(kern_ms, 5),
-            "eager_ms_per_step": round(eager_ms, 5),
+            "eager_ms_per_step": round(eager_ms, 5) if args.full else None,
             "kernel": kernel_name, "build_id": _abi.build_id(),
             "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
@@ -817,20 +872,24 @@ def run_primal(args, dist, rank, world, local):
     if dist:
         dist.barrier()
     wall_kern_ms = e0.elapsed_time(e1) / R  # stream interval per launch, host launch gaps included
-    # the kernel's own duration: the same launches again, each recording start / stop at
-    # the kernel's begin / end (mapfx_primal_act_timed, hipExtLaunchKernel); median
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(R)]
+    if args.dump_outputs and rank == 0:     # the last call of the last timed launch, per world
+        dump_outputs(args.dump_outputs, dict({k: v[:, -1] for k, v in b.out.items()}, pos=b.pos))
+    # the kernel's own duration (--full): the same launches again, each recording start /
+    # stop at the kernel's begin / end (mapfx_primal_act_timed, hipExtLaunchKernel); median
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+          for _ in range(R if args.full else 0)]
     for a0, a1 in ev:
         a0.record(stream)   # creates the HIP events
         a1.record(stream)
-    b.pos.copy_(pos0)
+    if args.full:
+        b.pos.copy_(pos0)
     for pr in ev:
         b.act(ids, acts, events=pr)
     torch.cuda.synchronize()
     from mapfx import _abi
     kernel_name = _abi.last_kernel()
     kern_list = sorted(a0.elapsed_time(a1) for a0, a1 in ev)
-    kern_ms = kern_list[len(kern_list) // 2]
+    kern_ms = kern_list[len(kern_list) // 2] if args.full else None
     el = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
     if dist:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
@@ -839,12 +898,8 @@ def run_primal(args, dist, rank, world, local):
     calls = E * world * KC * R
     bpc = primal_bytes_per_call(s_obs)
     launch_bytes = E * (KC * bpc + (8 + 8 + 8) * N + inst["bits"].shape[1])  # + pos/goal in, pos out
-    achieved = launch_bytes / (kern_ms * 1e-3) / 1e9
-    # the profile is keyed by what tools/pmc_traffic.py records: config, calls per launch
-    # (T) and worlds (E); the bench's fixed 32 x 32 / 16 agents / s = 10 shape is implied
-    traffic, traffic_src = profile_traffic("primal", kernel=kernel_name, config="primal", E=E, T=KC)
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         from oracle.primal_dyn_oracle import PrimalWorld
         ids_h, acts_h = ids.cpu().numpy(), acts.cpu().numpy()
         t_start, n, e = time.perf_counter(), 0, 0
@@ -861,7 +916,7 @@ def run_primal(args, dist, rank, world, local):
                "sample": "%d calls (%d worlds x %d) of the same workload: "
                          "oracle/primal_dyn_oracle.py PrimalWorld.step, %.1f s" % (n, e, KC, el_c)}
     if rank == 0:
-        print(json.dumps({
+        line = {
             "metric": "PRIMAL _step calls/sec (sequential single-agent dynamics + observation)",
             "value": round(calls / elapsed, 1), "unit": "agent-calls/s",
             "n_gpus": world, "steps": KC * R, "warmup": KC * RW,
@@ -873,18 +928,28 @@ def run_primal(args, dist, rank, world, local):
                                    "%d, %d _step calls per world per launch (%d launches)"
                                    % (E, N, s_obs, KC, R),
                        "envs_total": E * world, "agents": N, "parallelism": "env-shard x%d" % world},
-            "kernel_ms_per_launch": round(kern_ms, 5),
             "kernel": kernel_name, "build_id": _abi.build_id(),
-            "timing": {"kernel_ms_launches": [round(x, 5) for x in kern_list],
-                       "stream_ms_per_launch": round(wall_kern_ms, 5),
-                       "kernel_timing": "per-launch start/stop events recorded at the kernel's "
-                                        "begin/end (hipExtLaunchKernel) on %d launches right after "
-                                        "the timed region; median" % R},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "bytes_per_call": bpc, "bytes_per_launch": int(launch_bytes)},
-            "cpu_baseline": cpu}), flush=True)
+            "timing": {"stream_ms_per_launch": round(wall_kern_ms, 5)}}
+        if args.full:
+            achieved = launch_bytes / (kern_ms * 1e-3) / 1e9
+            # the profile is keyed by what tools/pmc_traffic.py records: config, calls per
+            # launch (T) and worlds (E); the bench's fixed 32 x 32 / 16 agents / s = 10 shape
+            # is implied
+            traffic, traffic_src = profile_traffic("primal", kernel=kernel_name, config="primal",
+                                                   E=E, T=KC)
+            line.update({
+                "kernel_ms_per_launch": round(kern_ms, 5),
+                "timing": {"kernel_ms_launches": [round(x, 5) for x in kern_list],
+                           "stream_ms_per_launch": round(wall_kern_ms, 5),
+                           "kernel_timing": "per-launch start/stop events recorded at the kernel's "
+                                            "begin/end (hipExtLaunchKernel) on %d launches right "
+                                            "after the timed region; median" % R},
+                "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+                             "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                             "traffic": traffic, "traffic_source": traffic_src,
+                             "bytes_per_call": bpc, "bytes_per_launch": int(launch_bytes)},
+                "cpu_baseline": cpu})
+        print(json.dumps(line), flush=True)
     if dist:
         dist.barrier()
         dist.destroy_process_group()
@@ -951,9 +1016,12 @@ def run_runner(args, dist, rank, world, local):
     t_env0 = runner.t_env
     t0 = time.perf_counter()
     for _ in range(runs):
-        runner.run()
+        batch = runner.run()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:     # the last run's episodes of the first 64 envs
+        dump_outputs(args.dump_outputs,
+                     {k: v[:64] for k, v in batch.data.transition_data.items()})
     steps = runner.t_env - t_env0
     el = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
     if dist:
@@ -961,7 +1029,7 @@ def run_runner(args, dist, rank, world, local):
         dist.barrier()
     elapsed = float(el.item())
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         cpu = partial_cpu_baseline(inst, S, N, args.cpu_seconds)
     # roofline of the runner step on the wall clock (the MAC's torch kernels and the
     # launch gaps included): per env step, the env step's own bytes plus the

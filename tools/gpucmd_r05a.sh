@@ -13,11 +13,11 @@ tail -3 $O/gpu_tests.txt
 if [ $rc -ne 0 ]; then grep -E "FAIL|Error|assert" $O/gpu_tests.txt | head -40; exit 1; fi
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.txt 2>&1 || { tail $O/smoke.txt; exit 1; }
 tail -1 $O/smoke.txt
-timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_c2_t20.json 2> $O/bench_c2_t20.err || { tail $O/bench_c2_t20.err; exit 1; }
+timeout -k 10 300 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_c2_t20.json 2> $O/bench_c2_t20.err || { tail $O/bench_c2_t20.err; exit 1; }
 python3 -c "import json; d=json.load(open('$O/bench_c2_t20.json')); print(d['value'], d['kernel_ms_per_launch'], d['kernel'][:80], d['build_id'], d['roofline']['traffic_source'])"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/c3_trace -o run --output-format csv \
-  -- python3 bench.py --config c3 --cpu-seconds 0 --per-step-steps 0 > $O/bench_c3_traced.json 2> $O/c3_trace.err || { tail $O/c3_trace.err; exit 1; }
-timeout -k 10 300 python3 bench.py --config c3 --cpu-seconds 0 --per-step-steps 0 > $O/bench_c3.json 2> $O/bench_c3.err || { tail $O/bench_c3.err; exit 1; }
+  -- python3 bench.py --full --config c3 --cpu-seconds 0 --per-step-steps 0 > $O/bench_c3_traced.json 2> $O/c3_trace.err || { tail $O/c3_trace.err; exit 1; }
+timeout -k 10 300 python3 bench.py --full --config c3 --cpu-seconds 0 --per-step-steps 0 > $O/bench_c3.json 2> $O/bench_c3.err || { tail $O/bench_c3.err; exit 1; }
 python3 - <<'PY'
 import csv, glob, json
 O = "gpurun_out/r05a"

@@ -10,7 +10,7 @@ OUT=r05aa bash tools/gpucmd_r05r.sh || exit 1
 for v in new old; do
   if [ $v = new ]; then L=""; else L=$PWD/varlibs/libmapfx_old.so; fi
   MAPFX_LIB=$L timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE -d $O/fetch_$v -o run --output-format csv \
-    -- python3 bench.py --env marl_partial --cpu-seconds 0 > $O/fetch_$v.json 2> $O/fetch_$v.err || { tail $O/fetch_$v.err; exit 1; }
+    -- python3 bench.py --full --env marl_partial --cpu-seconds 0 > $O/fetch_$v.json 2> $O/fetch_$v.err || { tail $O/fetch_$v.err; exit 1; }
   python3 - $O/fetch_$v <<'PY'
 import csv, glob, sys
 vals = []

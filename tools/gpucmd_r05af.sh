@@ -8,7 +8,7 @@ mkdir -p $O
 for rep in 1 2 3; do
   for v in new old; do
     if [ $v = new ]; then L=""; else L=$PWD/varlibs/libmapfx_old.so; fi
-    MAPFX_LIB=$L timeout -k 10 200 python3 bench.py --config c5 --cpu-seconds 0 --per-step-steps 0 > $O/c5_${v}_$rep.json 2> $O/c5_${v}_$rep.err || { tail $O/c5_${v}_$rep.err; exit 1; }
+    MAPFX_LIB=$L timeout -k 10 200 python3 bench.py --full --config c5 --cpu-seconds 0 --per-step-steps 0 > $O/c5_${v}_$rep.json 2> $O/c5_${v}_$rep.err || { tail $O/c5_${v}_$rep.err; exit 1; }
     python3 -c "import json; d=json.load(open('$O/c5_${v}_$rep.json')); print('$v $rep c5', d['kernel_ms_per_launch'], d['roofline']['frac'], d['kernel'][40:90])"
   done
 done

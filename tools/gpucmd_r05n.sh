@@ -8,8 +8,8 @@ mkdir -p $O
 for rep in 1 2 3; do
   for v in new lsv; do
     if [ $v = new ]; then L=""; else L=$PWD/varlibs/libmapfx_lsv.so; fi
-    MAPFX_LIB=$L timeout -k 10 200 python3 bench.py --env marl_partial --cpu-seconds 0 > $O/p_${v}_$rep.json 2> $O/p_${v}_$rep.err || { tail $O/p_${v}_$rep.err; exit 1; }
-    MAPFX_LIB=$L timeout -k 10 200 python3 bench.py --env runner --cpu-seconds 0 > $O/r_${v}_$rep.json 2> $O/r_${v}_$rep.err || { tail $O/r_${v}_$rep.err; exit 1; }
+    MAPFX_LIB=$L timeout -k 10 200 python3 bench.py --full --env marl_partial --cpu-seconds 0 > $O/p_${v}_$rep.json 2> $O/p_${v}_$rep.err || { tail $O/p_${v}_$rep.err; exit 1; }
+    MAPFX_LIB=$L timeout -k 10 200 python3 bench.py --full --env runner --cpu-seconds 0 > $O/r_${v}_$rep.json 2> $O/r_${v}_$rep.err || { tail $O/r_${v}_$rep.err; exit 1; }
     python3 -c "import json; p=json.load(open('$O/p_${v}_$rep.json')); r=json.load(open('$O/r_${v}_$rep.json')); print('$v $rep partial', p['ms_per_step'], p['roofline']['frac'], 'runner', r['ms_per_step'])"
   done
 done

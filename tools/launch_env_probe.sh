@@ -4,7 +4,7 @@
 set -o pipefail
 OUT=gpurun_out/launch_env
 mkdir -p $OUT
-B="--gpus 1 --steps 20 --warmup 5 --cpu-seconds 0 --per-step-steps 0"
+B="--gpus 1 --steps 20 --warmup 5 --full --cpu-seconds 0 --per-step-steps 0"
 run() {  # tag, env assignments...
   local tag=$1; shift
   for i in 1 2 3; do
@@ -22,7 +22,7 @@ run actwait ROC_ACTIVE_WAIT_TIMEOUT=100 || exit $?
 run kernarg0 HIP_FORCE_DEV_KERNARG=0 || exit $?
 run kernarg1 HIP_FORCE_DEV_KERNARG=1 || exit $?
 # per-step path: the default library vs one built with kernarg preload (16 SGPRs)
-P="--gpus 1 --steps 20 --warmup 5 --cpu-seconds 0 --per-step-steps 400"
+P="--gpus 1 --steps 20 --warmup 5 --full --cpu-seconds 0 --per-step-steps 400"
 for v in base preload16; do
   if [ $v = base ]; then unset MAPFX_LIB; else export MAPFX_LIB=$PWD/mapf-marl_amd/mapfx/libmapfx_$v.so; fi
   timeout -k 10 120 python3 bench.py $P > $OUT/ps_$v.json 2> $OUT/ps_$v.err || exit $?

@@ -185,7 +185,7 @@ def main():
                     help="bench line of the profiled command: exact kernel instance + build id")
     ap.add_argument("--bench-kernel-key", default="kernel",
                     help="dotted key of the kernel name in the bench line (per_step.kernel for the "
-                         "per-step leg)")
+                         "per-step leg, which bench.py runs under --full)")
     ap.add_argument("--match", action="append", default=[],
                     help="key=int stored in the summary (bench.py only uses a profile whose "
                          "keys equal its workload's)")

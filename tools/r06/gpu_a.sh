@@ -10,5 +10,5 @@ timeout -k 10 900 python3 -u -m pytest tests/test_gpu_parity.py -m gpu -x -v --t
 rc=$?
 tail -3 $O/tests.txt
 if [ $rc -ne 0 ]; then grep -E "FAIL|Error|assert" $O/tests.txt | head -40; exit 1; fi
-timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 > $O/bench_c2_t20.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
+timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 > $O/bench_c2_t20.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
 tail -c 600 $O/bench_c2_t20.json

@@ -13,7 +13,7 @@ tail -2 $O/tests.txt
 for rep in 1 2 3; do
   for v in new sep; do
     if [ $v = new ]; then L=""; else L=$PWD/varlibs/libmapfx_sepcmp.so; fi
-    MAPFX_LIB=$L timeout -k 10 200 python3 bench.py --env runner --cpu-seconds 0 > $O/runner_${v}_$rep.json 2> $O/runner_${v}_$rep.err || { tail $O/runner_${v}_$rep.err; exit 1; }
+    MAPFX_LIB=$L timeout -k 10 200 python3 bench.py --full --env runner --cpu-seconds 0 > $O/runner_${v}_$rep.json 2> $O/runner_${v}_$rep.err || { tail $O/runner_${v}_$rep.err; exit 1; }
     python3 -c "import json; d=json.load(open('$O/runner_${v}_$rep.json')); print('$v $rep runner', d['ms_per_step'], d['value'])"
   done
 done

@@ -10,7 +10,7 @@ for rep in 1 2 3; do
   for v in new chkrt; do
     if [ $v = new ]; then L=""; else L=$PWD/varlibs/libmapfx_chkrt.so; fi
     for T in 20 64; do
-      MAPFX_LIB=$L timeout -k 10 200 python3 bench.py --steps $T --warmup 5 --chunk 64 --cpu-seconds 0 --per-step-steps 0 > $O/c2_${v}_T${T}_$rep.json 2> $O/c2_${v}_T${T}_$rep.err || { tail $O/c2_${v}_T${T}_$rep.err; exit 1; }
+      MAPFX_LIB=$L timeout -k 10 200 python3 bench.py --full --steps $T --warmup 5 --chunk 64 --cpu-seconds 0 --per-step-steps 0 > $O/c2_${v}_T${T}_$rep.json 2> $O/c2_${v}_T${T}_$rep.err || { tail $O/c2_${v}_T${T}_$rep.err; exit 1; }
       python3 -c "import json; d=json.load(open('$O/c2_${v}_T${T}_$rep.json')); print('$v T$T $rep', d['kernel_ms_per_launch'], d['roofline']['frac'], d['ms_per_step'])"
     done
   done

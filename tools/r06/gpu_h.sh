@@ -13,7 +13,7 @@ for rep in 1 2 3; do
   for v in new pre64; do
     if [ $v = new ]; then L=""; else L=$PWD/varlibs/libmapfx_pre64.so; fi
     for T in 64 20; do
-      MAPFX_LIB=$L timeout -k 10 200 python3 bench.py --config c3 --steps $T --warmup 5 --chunk 64 --cpu-seconds 0 --per-step-steps 0 > $O/c3_${v}_T${T}_$rep.json 2> $O/c3_${v}_T${T}_$rep.err || { tail $O/c3_${v}_T${T}_$rep.err; exit 1; }
+      MAPFX_LIB=$L timeout -k 10 200 python3 bench.py --full --config c3 --steps $T --warmup 5 --chunk 64 --cpu-seconds 0 --per-step-steps 0 > $O/c3_${v}_T${T}_$rep.json 2> $O/c3_${v}_T${T}_$rep.err || { tail $O/c3_${v}_T${T}_$rep.err; exit 1; }
       python3 -c "import json; d=json.load(open('$O/c3_${v}_T${T}_$rep.json')); print('$v c3 T$T $rep', d['kernel_ms_per_launch'], d['roofline']['frac'], d['kernel'][40:90])"
     done
   done

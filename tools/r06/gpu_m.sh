@@ -11,7 +11,7 @@ for v in shipped nolookup; do
   if [ $v = shipped ]; then L=""; else L=$PWD/varlibs/libmapfx_nolookup.so; fi
   for c in FETCH_SIZE WRITE_SIZE; do
     MAPFX_LIB=$L timeout -s KILL 120 rocprofv3 --pmc $c -d $O/${v}_$c -o run --output-format csv \
-      -- python3 bench.py --env marl_partial --cpu-seconds 0 > $O/${v}_$c.json 2> $O/${v}_$c.err || { tail $O/${v}_$c.err; exit 1; }
+      -- python3 bench.py --full --env marl_partial --cpu-seconds 0 > $O/${v}_$c.json 2> $O/${v}_$c.err || { tail $O/${v}_$c.err; exit 1; }
   done
   python3 -c "import json; d=json.load(open('$O/${v}_FETCH_SIZE.json')); print('$v kernel_ms_per_step', d['kernel_ms_per_step'])"
 done

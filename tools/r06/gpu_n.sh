@@ -6,7 +6,7 @@ set -o pipefail
 export TMPDIR=/tmp
 O=gpurun_out/r06n
 mkdir -p $O
-timeout -k 10 300 python3 bench.py --gpus 2 --rehearse-shared-gpu --steps 40 --warmup 20 --chunk 20 --cpu-seconds 0 --per-step-steps 0 > $O/rehearse.json 2> $O/rehearse.err || { tail $O/rehearse.err; exit 1; }
+timeout -k 10 300 python3 bench.py --full --gpus 2 --rehearse-shared-gpu --steps 40 --warmup 20 --chunk 20 --cpu-seconds 0 --per-step-steps 0 > $O/rehearse.json 2> $O/rehearse.err || { tail $O/rehearse.err; exit 1; }
 python3 -c "import json; d=json.load(open('$O/rehearse.json')); print(d['n_gpus'], d['config']['parallelism'], d['gather']['collective'])"
 timeout -k 10 1000 python3 -u -m pytest tests -m gpu -q --timeout 300 --timeout-method thread > $O/gpu_tests.txt 2>&1
 rc=$?

@@ -13,10 +13,10 @@ for rep in 1 2 3; do
   for v in new base; do
     if [ $v = new ]; then L=""; else L=$PWD/varlibs/libmapfx_base.so; fi
     for T in 20 64; do
-      MAPFX_LIB=$L timeout -k 10 200 python3 bench.py --steps $T --warmup 5 --chunk 64 --cpu-seconds 0 --per-step-steps 200 > $O/c2_${v}_T${T}_$rep.json 2> $O/c2_${v}_T${T}_$rep.err || { tail $O/c2_${v}_T${T}_$rep.err; exit 1; }
+      MAPFX_LIB=$L timeout -k 10 200 python3 bench.py --full --steps $T --warmup 5 --chunk 64 --cpu-seconds 0 --per-step-steps 200 > $O/c2_${v}_T${T}_$rep.json 2> $O/c2_${v}_T${T}_$rep.err || { tail $O/c2_${v}_T${T}_$rep.err; exit 1; }
       python3 -c "import json; d=json.load(open('$O/c2_${v}_T${T}_$rep.json')); print('$v c2 T$T $rep', d['kernel_ms_per_launch'], d['ms_per_step'], 'per_step', d['per_step']['kernel_ms'], d['per_step']['ms_per_step'])"
     done
-    MAPFX_LIB=$L timeout -k 10 200 python3 bench.py --config c3 --steps 64 --warmup 5 --chunk 64 --cpu-seconds 0 --per-step-steps 0 > $O/c3_${v}_$rep.json 2> $O/c3_${v}_$rep.err || { tail $O/c3_${v}_$rep.err; exit 1; }
+    MAPFX_LIB=$L timeout -k 10 200 python3 bench.py --full --config c3 --steps 64 --warmup 5 --chunk 64 --cpu-seconds 0 --per-step-steps 0 > $O/c3_${v}_$rep.json 2> $O/c3_${v}_$rep.err || { tail $O/c3_${v}_$rep.err; exit 1; }
     python3 -c "import json; d=json.load(open('$O/c3_${v}_$rep.json')); print('$v c3 T64 $rep', d['kernel_ms_per_launch'], d['ms_per_step'])"
   done
 done

@@ -12,7 +12,7 @@ tail -2 $O/tests.txt
 for rep in 1 2 3; do
   for v in new base; do
     if [ $v = new ]; then L=""; else L=$PWD/varlibs/libmapfx_base.so; fi
-    MAPFX_LIB=$L timeout -k 10 200 python3 bench.py --config c5 --steps 64 --warmup 5 --chunk 64 --cpu-seconds 0 --per-step-steps 0 > $O/c5_${v}_$rep.json 2> $O/c5_${v}_$rep.err || { tail $O/c5_${v}_$rep.err; exit 1; }
+    MAPFX_LIB=$L timeout -k 10 200 python3 bench.py --full --config c5 --steps 64 --warmup 5 --chunk 64 --cpu-seconds 0 --per-step-steps 0 > $O/c5_${v}_$rep.json 2> $O/c5_${v}_$rep.err || { tail $O/c5_${v}_$rep.err; exit 1; }
     python3 -c "import json; d=json.load(open('$O/c5_${v}_$rep.json')); print('$v c5 T64 $rep', d['kernel_ms_per_launch'], d['ms_per_step'], d['roofline']['frac'])"
   done
 done

@@ -11,7 +11,7 @@ tail -2 $O/tests.txt
 for rep in 1 2 3; do
   for v in prefetch reset; do
     if [ $v = prefetch ]; then F=""; else F="--no-batch-prefetch"; fi
-    timeout -k 10 300 python3 bench.py --env runner $F > $O/runner_${v}_$rep.json 2> $O/runner_${v}_$rep.err || { tail $O/runner_${v}_$rep.err; exit 1; }
+    timeout -k 10 300 python3 bench.py --full --env runner $F > $O/runner_${v}_$rep.json 2> $O/runner_${v}_$rep.err || { tail $O/runner_${v}_$rep.err; exit 1; }
     python3 -c "import json; d=json.load(open('$O/runner_${v}_$rep.json')); print('$v', $rep, d['value'], d['ms_per_step'])"
   done
 done
