@@ -19,9 +19,15 @@
  * each agent's past position (agents_past) is part of the state, updated by a stay
  * and by a successful move (:110-112, :129-131), and next_mask has 9 bits (u16).
  * JOINT = False (the reference default, :27).
- * The stay-on-goal blocking term (:583, get_blocking_reward) needs the
- * un-vendored od_mstar3 planner and is defined as 0 (parity unpinned); the
- * `blocking` output of _step is therefore always False and not produced.
+ * The stay-on-goal blocking term (:583, get_blocking_reward :513-546) is 0 unless the
+ * blocking pass (mapfx_primal_blocking, after mapfx_primal_act) is run: then a stay on
+ * the goal gets GOAL_REWARD + num_blocking * BLOCKING_COST and `blocking` is produced.
+ * The reference asks the od_mstar3 planner for one robot's path at inflation 1 and uses
+ * only its length and "no solution"; the pass assumes that planner returns optimal
+ * 4-connected paths (also with DIAGONAL_MOVEMENT: the planner is called the same way),
+ * so the lengths are BFS distances + 1 -- parity is pinned up to the planner.  Not
+ * modelled: the planner's 5 s time limit / OutOfTimeError; JOINT stays False.  As in the
+ * reference (`range(1, num_agents)`, :523) the last agent is never examined.
  * Agents start on free cells (PRIMAL keeps agents and obstacles in one array).
  *
  * Same conventions as mapfx.h: caller-owned DEVICE pointers, asynchronous on
@@ -86,6 +92,26 @@ int mapfx_primal_act(mapfx_primal_t* h, const mapfx_primal_state* st, const int3
 int mapfx_primal_act_timed(mapfx_primal_t* h, const mapfx_primal_state* st, const int32_t* agent_ids,
                            const int32_t* actions, int32_t K, const mapfx_primal_out* out,
                            void* start_event, void* stop_event, void* stream);
+
+/* get_blocking_reward(agent_ids[e]) (:513-546) of every world at st->pos as it stands
+ * (the agent need not be on its goal, as in the reference): counts[e] = num_blocking
+ * (0 for an id outside 1..N). */
+int mapfx_primal_blocking_count(mapfx_primal_t* h, const mapfx_primal_state* st,
+                                const int32_t* agent_ids /* [E], 1-based */,
+                                int32_t* counts /* [E] */, void* stream);
+
+/* The blocking term of the K calls a mapfx_primal_act launch has just made: same h,
+ * agent_ids, actions and K, same stream, st->pos as that launch left it, valid /
+ * on_goal as it wrote them.  For every executed call with action 0 and on_goal 1:
+ * reward[e][k] = 0.0 + n * -1.0, blocking[e][k] = n > 0, counts[e][k] = n; every
+ * other element of the three arrays: reward untouched, blocking = 0, counts = 0.
+ * reward, blocking, counts may each be NULL (not produced); valid and on_goal not.
+ * The world call k saw is st->pos with the valid moves of the later calls undone; a
+ * world that mapfx_primal_act stopped at a bad (agent, action) stops here too. */
+int mapfx_primal_blocking(mapfx_primal_t* h, const mapfx_primal_state* st,
+                          const int32_t* agent_ids, const int32_t* actions, int32_t K,
+                          const uint8_t* valid, const uint8_t* on_goal,
+                          double* reward, uint8_t* blocking, int32_t* counts, void* stream);
 
 #ifdef __cplusplus
 }

@@ -333,7 +333,8 @@ __global__ void __launch_bounds__(64) primal_act_kernel(QGeo g, QArgs a) {
         }
       }
       if (ag == 0) {
-        // ---- reward (:579-596), JOINT = False; stay-on-goal blocking term = 0 ----
+        // ---- reward (:579-596), JOINT = False; the stay-on-goal blocking term is added
+        //      afterwards by mapfx_primal_blocking (0 when that pass is not run) ----
         const double rew = act == 0 ? (status == 1 ? GOAL_REWARD + 0 : IDLE_COST)
                                     : status == 1 ? GOAL_REWARD : status < 0 ? COLLISION_REWARD : ACTION_COST;
         const int j = k - kb;
@@ -721,11 +722,14 @@ struct mapfx_primal_t {
   QGeo geo;  // (seq layout included)
   double* pow_lut;
   int lds;
+  int blocking_flat;  // MAPFX_PRIMAL_BLOCKING=flat: the flat-set blocking kernel at every shape
 };
 
 namespace {
 
 using PrimalFn = void (*)(QGeo, QArgs);
+struct BArgs;
+using PrimalBFn = void (*)(QGeo, BArgs);
 
 template <int S, int LS, bool DIAG>
 PrimalFn pick_ma(int apl) {
@@ -792,6 +796,326 @@ int layout(QGeo& g) {
   g.off_fst = o;
   o += 5 * 64;
   return r16(o);
+}
+
+// ---------------------------------------------------------------------------
+// primal_blocking_kernel<ROWS>: get_blocking_reward (:513-546), one 64-lane workgroup
+// per (world, call).
+//
+// The reference asks its planner for ONE robot's optimal 4-connected path twice per
+// examined agent j (astar :501-511): with the sitter's cell as an obstacle ("before")
+// and without it ("after"), and uses only the two lengths and "no solution".  On an
+// unweighted grid that is a pair of BFS distances, so both searches run here as
+// bit-parallel floods that share one level loop: "after" stops at its goal level d,
+// "before" is cut at level d + 10 (inflation, :519), no distance table is written and
+// nothing per level leaves the workgroup.  The level counter is a plain int (a
+// serpentine 128 x 128 has paths of thousands of levels).
+//
+//   ROWS (H <= 64 and W <= 64): lane r holds row r as a 64-bit mask, as
+//     partial_bfs_kernel does: left / right are shifts, up / down come from lanes
+//     r - 1 / r + 1; the visible robots' row masks are built once per call in LDS.
+//   otherwise: one flat H * W-bit set (cell r * W + c = bit, the layout of the obstacle
+//     bitmap), up to 256 64-bit words, word lane + 64 t in lane's registers, published
+//     to LDS once per level for the neighbours' reads; left / right are shifts by 1
+//     under row-edge masks, up / down shifts by W across words.
+//
+// With a.undo the world call k saw is rebuilt from st->pos after the launch: the valid
+// moves of calls k + 1 .. kstop - 1 are subtracted (kstop: the world's first bad call,
+// the range test of primal_act_kernel), which needs no order -- the sum of an agent's
+// undone moves is the same in any.
+// ---------------------------------------------------------------------------
+constexpr int BLOCK_INFLATION = 10;   // :519
+constexpr double BLOCKING_COST = -1.;  // :25
+
+struct BArgs {
+  const int32_t* pos;
+  const int32_t* goal;
+  const uint8_t* bits;
+  const int32_t* ids;
+  const int32_t* acts;
+  int K;
+  const uint8_t* valid;
+  const uint8_t* on_goal;
+  double* reward;
+  uint8_t* blocking;
+  int32_t* counts;
+  int undo;  // 1: the K calls of an act launch; 0: agent ids[e] at st->pos as it stands (K = 1)
+};
+
+// x[i], 0 outside 0 .. nw - 1 (a clamped read and a select: no branch around the load)
+__device__ inline uint64_t bw_get(const uint64_t* x, int i, int nw) {
+  const uint64_t v = x[min(max(i, 0), nw - 1)];
+  return (unsigned)i < (unsigned)nw ? v : 0ull;
+}
+// word w of the set x moved by +(64 q + r) / -(64 q + r) cells (0 <= r < 64)
+__device__ inline uint64_t bw_up(const uint64_t* x, int w, int q, int r, int nw) {
+  const uint64_t lo = bw_get(x, w - q - 1, nw) >> ((64 - r) & 63);
+  return (bw_get(x, w - q, nw) << r) | (r ? lo : 0ull);
+}
+__device__ inline uint64_t bw_down(const uint64_t* x, int w, int q, int r, int nw) {
+  const uint64_t hi = bw_get(x, w + q + 1, nw) << ((64 - r) & 63);
+  return (bw_get(x, w + q, nw) >> r) | (r ? hi : 0ull);
+}
+// the 4-connected neighbours of the set x, word w (not yet masked by the free cells)
+__device__ inline uint64_t bw_nbr(const uint64_t* x, int w, int nw, int q, int r, uint64_t nc0, uint64_t ncl) {
+  return (bw_up(x, w, 0, 1, nw) & nc0) | (bw_down(x, w, 0, 1, nw) & ncl) | bw_up(x, w, q, r, nw) |
+         bw_down(x, w, q, r, nw);
+}
+// the neighbours of the rows x (lane = row): same row by shifts, rows r - 1 / r + 1 by shuffles
+__device__ inline uint64_t row_nbr(uint64_t x, int lane) {
+  const uint64_t up = __shfl_up(x, 1), dn = __shfl_down(x, 1);
+  return (x << 1) | (x >> 1) | (lane > 0 ? up : 0ull) | (lane < 63 ? dn : 0ull);
+}
+
+// After level L of the two floods (gA / gB: the goal is in the flood, chA / chB: the
+// flood grew; "after" is no longer advanced once found): 0 go on, 1 not blocked, 2 blocked.
+__device__ inline int bw_verdict(bool& foundA, int& dA, int L, bool gA, bool chA, bool gB, bool chB) {
+  if (!foundA) {
+    if (__ballot(gA)) foundA = true, dA = L;
+    else if (!__ballot(chA)) return 1;  // "after" died out: no path either way (:541-542)
+  }
+  if (__ballot(gB)) return 1;           // "before" arrives by level d_after + 10
+  if (foundA && (L >= dA + BLOCK_INFLATION || !__ballot(chB))) return 2;  // (:543-545)
+  return 0;
+}
+
+template <bool ROWS>
+__global__ void __launch_bounds__(64) primal_blocking_kernel(QGeo g, BArgs a) {
+  extern __shared__ __align__(16) unsigned char lds[];
+  constexpr int WPL = 4;  // flat words per lane: H * W <= 16384 = 4 * 64 * 64
+  const int lane = threadIdx.x, K = a.K, N = g.N, H = g.H, W = g.W;
+  const int e = (int)(blockIdx.x / (unsigned)K), k = (int)(blockIdx.x - (unsigned)e * (unsigned)K);
+  const long long e0k = (long long)e * K, oi = e0k + k;
+  const int nw = ROWS ? 64 : (g.hw + 63) >> 6;
+  uint64_t* fre = (uint64_t*)lds;  // ROWS: [64] the visible robots' rows; flat: the free cells
+  uint64_t* nc0 = fre + nw;        // flat only: cells not in column 0
+  uint64_t* ncl = nc0 + nw;        //            cells not in column W - 1
+  uint64_t* curA = ncl + nw;       //            the "after" / "before" floods of the level
+  uint64_t* curB = curA + nw;
+  int* posr = (int*)(ROWS ? fre + nw : curB + nw);  // [N] rows, [N] columns of the world at this call
+  int* posc = posr + N;
+  int2* goalL = (int2*)(posc + N);                  // [N] goals
+
+  int n = 0, aid = 0;
+  bool run = true;
+  if (a.undo)  // a stay (action 0) on the goal, two loads; everything else leaves at once
+    run = a.acts[oi] == 0 && a.on_goal[oi] != 0;
+  uint64_t frow = 0;  // ROWS: the cells of row `lane` without a wall
+  if (run) {
+    // ---- set-up.  Everything the call needs from global memory is loaded before the
+    //      first use (one round trip): the sitter, the first 64 calls of the world,
+    //      positions, goals, the map ----
+    aid = a.ids[oi] - 1;
+    int id0 = 0, ac0 = 0, va0 = 0;
+    if (a.undo && lane < K) {
+      id0 = a.ids[e0k + lane];
+      ac0 = a.acts[e0k + lane];
+      va0 = a.valid[e0k + lane];
+    }
+    int2 pp[WPL], gg[WPL];  // N <= 255: at most 4 agents per lane
+#pragma unroll
+    for (int t = 0; t < WPL; ++t) {
+      const int i = lane + 64 * t;
+      if (i < N) {
+        pp[t] = ((const int2*)a.pos)[(long long)e * N + i];
+        gg[t] = ((const int2*)a.goal)[(long long)e * N + i];
+      }
+    }
+    const uint32_t* src = (const uint32_t*)(a.bits + (g.map_shared ? 0 : (long long)e * g.map_stride));
+    if constexpr (ROWS) {
+      if (lane < H) {
+        const int b0 = lane * W, wi = b0 >> 5, sh = b0 & 31, last = (b0 + W - 1) >> 5;
+        const uint64_t d0 = src[wi], d1 = wi + 1 <= last ? src[wi + 1] : 0u, d2 = wi + 2 <= last ? src[wi + 2] : 0u;
+        uint64_t v = (d0 | (d1 << 32)) >> sh;
+        if (sh) v |= d2 << (64 - sh);
+        frow = ~v & (W == 64 ? ~0ull : (1ull << W) - 1ull);
+      }
+      fre[lane] = 0ull;
+    } else {
+      uint64_t wl[WPL];
+#pragma unroll
+      for (int t = 0; t < WPL; ++t) {
+        const int w = lane + 64 * t;
+        if (w < nw) wl[t] = (uint64_t)src[2 * w] | ((uint64_t)(2 * w + 1 < g.bits_words ? src[2 * w + 1] : 0u) << 32);
+      }
+#pragma unroll
+      for (int t = 0; t < WPL; ++t) {
+        const int w = lane + 64 * t;
+        if (w < nw) {
+          const int rem = g.hw - 64 * w;
+          fre[w] = ~wl[t] & (rem >= 64 ? ~0ull : (1ull << rem) - 1ull);
+          nc0[w] = ~0ull;
+          ncl[w] = ~0ull;
+        }
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < WPL; ++t) {
+      const int i = lane + 64 * t;
+      if (i < N) {
+        posr[i] = pp[t].x;
+        posc[i] = pp[t].y;
+        goalL[i] = gg[t];
+      }
+    }
+    wave_fence();
+    if constexpr (!ROWS)
+      for (int r = lane; r < H; r += 64) {
+        const int i0 = r * W, i1 = i0 + W - 1;
+        atomicAnd((unsigned int*)nc0 + (i0 >> 5), ~(1u << (i0 & 31)));
+        atomicAnd((unsigned int*)ncl + (i1 >> 5), ~(1u << (i1 & 31)));
+      }
+    if (a.undo) {
+      // the world's first bad call kstop (:556-558; later calls were not executed, their
+      // valid / on_goal are stale), and the valid moves of calls k + 1 .. kstop - 1 undone
+      // (moved by the action's direction; a stay moves nothing)
+      int kstop = K;
+      for (int kb = 0; kb < K && kstop == K; kb += 64) {
+        const int j = kb + lane;
+        int id = id0, ac = ac0, va = va0;
+        if (kb > 0 && j < K) {
+          id = a.ids[e0k + j];
+          ac = a.acts[e0k + j];
+          va = a.valid[e0k + j];
+        }
+        const bool bad = j < K && !((unsigned)(id - 1) < (unsigned)N && (unsigned)ac < (unsigned)g.nact);
+        const uint64_t m = __ballot(bad);
+        if (m) kstop = kb + (int)__ffsll((unsigned long long)m) - 1;
+        if (j > k && j < kstop && va) {
+          atomicSub(&posr[id - 1], dir_r(ac));
+          atomicSub(&posc[id - 1], dir_c(ac));
+        }
+      }
+      run = k < kstop;
+    }
+    run = run && (unsigned)aid < (unsigned)N;
+    wave_fence();
+  }
+  if (run) {
+    // ---- the window of the sitter (:520-522) and the visible robots 1 .. N - 1 (:523-529:
+    //      the loop is range(1, num_agents), so the last agent is neither examined nor an
+    //      obstacle) ----
+    const int sr = posr[aid], sc = posc[aid];
+    const int tr = sr - g.s / 2, tc = sc - g.s / 2;
+    auto seen = [&](int r, int c) {
+      return r >= tr && r < tr + g.s && c >= tc && c < tc + g.s && (unsigned)r < (unsigned)H &&
+             (unsigned)c < (unsigned)W;
+    };
+    for (int i = lane; i < N - 1; i += 64)
+      if (i != aid && seen(posr[i], posc[i])) {
+        if constexpr (ROWS) {
+          atomicOr((unsigned int*)(fre + posr[i]) + (posc[i] >> 5), 1u << (posc[i] & 31));
+        } else {
+          const int idx = posr[i] * W + posc[i];
+          atomicAnd((unsigned int*)fre + (idx >> 5), ~(1u << (idx & 31)));
+        }
+      }
+    wave_fence();
+    const bool sin = (unsigned)sr < (unsigned)H && (unsigned)sc < (unsigned)W;
+    if constexpr (ROWS) frow &= ~fre[lane];
+    const int q = W >> 6, r = W & 63;
+    for (int j = 0; j < N - 1; ++j) {  // (everything below is uniform over the wave)
+      if (j == aid) continue;
+      const int pr = posr[j], pc = posc[j];
+      if (!seen(pr, pc)) continue;
+      const int2 gj = goalL[j];
+      if ((unsigned)gj.x >= (unsigned)H || (unsigned)gj.y >= (unsigned)W) continue;
+      if (pr == gj.x && pc == gj.y) continue;  // both lengths 1
+      // "after": walls + the other visible robots; "before": the same + the sitter's cell
+      int verdict = 0;
+      if constexpr (ROWS) {
+        const uint64_t pb = lane == pr ? 1ull << pc : 0ull, gb = lane == gj.x ? 1ull << gj.y : 0ull;
+        const uint64_t fA = frow | pb, fB = fA & ~(sin && lane == sr ? 1ull << sc : 0ull);
+        if (!__ballot((fA & gb) != 0)) continue;  // the goal cell is an obstacle: no path after
+        uint64_t RA = pb, RB = pb;
+        bool foundA = false;
+        int dA = 0;
+        for (int L = 1; !verdict; ++L) {
+          bool chA = false, gA = false;
+          if (!foundA) {
+            const uint64_t nr = RA | (row_nbr(RA, lane) & fA);
+            chA = nr != RA;
+            RA = nr;
+            gA = (nr & gb) != 0;
+          }
+          const uint64_t nr = RB | (row_nbr(RB, lane) & fB);
+          const bool chB = nr != RB;
+          RB = nr;
+          verdict = bw_verdict(foundA, dA, L, gA, chA, (nr & gb) != 0, chB);
+        }
+      } else {
+        const int pidx = pr * W + pc, gidx = gj.x * W + gj.y, sidx = sin ? sr * W + sc : -1;
+        uint64_t fA[WPL], fB[WPL], RA[WPL], RB[WPL], m0[WPL], ml[WPL], gb[WPL];
+        bool gfree = false;
+#pragma unroll
+        for (int t = 0; t < WPL; ++t) {
+          const int w = lane + 64 * t;
+          const bool in = w < nw;
+          const uint64_t pb = (pidx >> 6) == w ? 1ull << (pidx & 63) : 0ull;
+          const uint64_t sb = (sidx >> 6) == w && sidx >= 0 ? 1ull << (sidx & 63) : 0ull;
+          gb[t] = (gidx >> 6) == w ? 1ull << (gidx & 63) : 0ull;
+          fA[t] = (in ? fre[w] : 0ull) | pb;
+          fB[t] = fA[t] & ~sb;
+          RA[t] = RB[t] = pb;
+          m0[t] = in ? nc0[w] : 0ull;
+          ml[t] = in ? ncl[w] : 0ull;
+          gfree |= (fA[t] & gb[t]) != 0;
+        }
+        if (!__ballot(gfree)) continue;  // the goal cell is an obstacle: no path after
+        bool foundA = false;
+        int dA = 0;
+        for (int L = 1; !verdict; ++L) {
+          bool chA = false, chB = false, gA = false, gB = false;
+#pragma unroll
+          for (int t = 0; t < WPL; ++t) {
+            const int w = lane + 64 * t;
+            if (w < nw) {
+              curA[w] = RA[t];
+              curB[w] = RB[t];
+            }
+          }
+          wave_fence();
+#pragma unroll
+          for (int t = 0; t < WPL; ++t) {
+            const int w = lane + 64 * t;
+            if (w < nw) {
+              if (!foundA) {
+                const uint64_t nr = RA[t] | (bw_nbr(curA, w, nw, q, r, m0[t], ml[t]) & fA[t]);
+                chA |= nr != RA[t];
+                RA[t] = nr;
+                gA |= (nr & gb[t]) != 0;
+              }
+              const uint64_t nr = RB[t] | (bw_nbr(curB, w, nw, q, r, m0[t], ml[t]) & fB[t]);
+              chB |= nr != RB[t];
+              RB[t] = nr;
+              gB |= (nr & gb[t]) != 0;
+            }
+          }
+          wave_fence();
+          verdict = bw_verdict(foundA, dA, L, gA, chA, gB, chB);
+        }
+      }
+      n += verdict == 2 ? 1 : 0;
+    }
+  }
+  if (lane == 0) {
+    if (run && a.reward) a.reward[oi] = GOAL_REWARD + n * BLOCKING_COST;  // (:581-583)
+    if (a.blocking) a.blocking[oi] = n > 0 ? 1 : 0;
+    if (a.counts) a.counts[oi] = n;
+  }
+}
+
+int launch_blocking(mapfx_primal_t* h, const BArgs& a, void* stream) {
+  const QGeo& g = h->geo;
+  if ((long long)g.E * a.K > 0x7FFFFFFFll) return perr(MAPFX_EINVAL, "n_envs * K too large");
+  // lane-per-row masks wherever the grid fits 64 x 64, unless a test pins the flat-set
+  // kernel (MAPFX_PRIMAL_BLOCKING=flat at mapfx_primal_create)
+  const bool rows = g.H <= 64 && g.W <= 64 && !h->blocking_flat;
+  const int lds = (rows ? 64 * 8 : (g.hw + 63) / 64 * 8 * 5) + g.N * 16;  // + positions, goals
+  const PrimalBFn fn = rows ? primal_blocking_kernel<true> : primal_blocking_kernel<false>;
+  hipLaunchKernelGGL(fn, dim3((unsigned)(g.E * a.K)), dim3(64), lds, (hipStream_t)stream, g, a);
+  mapfx_note_kernel((const void*)fn);
+  return check_hip(hipGetLastError(), "primal_blocking_kernel launch");
 }
 
 }  // namespace
@@ -862,6 +1186,10 @@ int mapfx_primal_create(const mapfx_primal_cfg* cfg, mapfx_primal_t** out) {
   g.apl = (g.N + g.lw - 1) / g.lw;
   g.wreg = wreg;
   h->lds = (64 >> ls) * wreg;
+  {
+    const char* bp = getenv("MAPFX_PRIMAL_BLOCKING");
+    h->blocking_flat = bp && strcmp(bp, "flat") == 0;
+  }
   if (h->lds > 64 * 1024) {
     const hipError_t e = hipFuncSetAttribute((const void*)pick_primal(g),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, h->lds);
@@ -947,6 +1275,49 @@ int mapfx_primal_act_timed(mapfx_primal_t* h, const mapfx_primal_state* st, cons
 int mapfx_primal_act(mapfx_primal_t* h, const mapfx_primal_state* st, const int32_t* agent_ids,
                      const int32_t* actions, int32_t K, const mapfx_primal_out* out, void* stream) {
   return mapfx_primal_act_timed(h, st, agent_ids, actions, K, out, nullptr, nullptr, stream);
+}
+
+int mapfx_primal_blocking_count(mapfx_primal_t* h, const mapfx_primal_state* st, const int32_t* agent_ids,
+                                int32_t* counts, void* stream) {
+  if (!h) return perr(MAPFX_EINVAL, "NULL handle");
+  if (!st || !st->pos || !st->goal || !st->map_bits) return perr(MAPFX_EINVAL, "bad state");
+  if (!agent_ids || !counts) return perr(MAPFX_EINVAL, "NULL agent_ids / counts");
+  if (h->geo.E == 0) return MAPFX_OK;
+  BArgs a;
+  memset(&a, 0, sizeof(a));
+  a.pos = st->pos;
+  a.goal = st->goal;
+  a.bits = st->map_bits;
+  a.ids = agent_ids;
+  a.K = 1;
+  a.counts = counts;
+  return launch_blocking(h, a, stream);
+}
+
+int mapfx_primal_blocking(mapfx_primal_t* h, const mapfx_primal_state* st, const int32_t* agent_ids,
+                          const int32_t* actions, int32_t K, const uint8_t* valid, const uint8_t* on_goal,
+                          double* reward, uint8_t* blocking, int32_t* counts, void* stream) {
+  if (!h) return perr(MAPFX_EINVAL, "NULL handle");
+  if (!st || !st->pos || !st->goal || !st->map_bits) return perr(MAPFX_EINVAL, "bad state");
+  if (K < 0) return perr(MAPFX_EINVAL, "K < 0");
+  if (!valid || !on_goal) return perr(MAPFX_EINVAL, "the blocking pass needs the launch's valid and on_goal");
+  if (K == 0 || h->geo.E == 0) return MAPFX_OK;
+  if (!agent_ids || !actions) return perr(MAPFX_EINVAL, "NULL agent_ids / actions");
+  BArgs a;
+  memset(&a, 0, sizeof(a));
+  a.pos = st->pos;
+  a.goal = st->goal;
+  a.bits = st->map_bits;
+  a.ids = agent_ids;
+  a.acts = actions;
+  a.K = K;
+  a.valid = valid;
+  a.on_goal = on_goal;
+  a.reward = reward;
+  a.blocking = blocking;
+  a.counts = counts;
+  a.undo = 1;
+  return launch_blocking(h, a, stream);
 }
 
 }  // extern "C"

@@ -7,6 +7,10 @@ one `State.moveAgent` (:103-135), the reward table (:579-596), `_observe`
 (:343-386), `State.done` (:159-166) and `_listNextValidActions` (:639-667), all
 in one HIP kernel.  `MAPFEnv` below is the single-world drop-in with the
 reference's call signature.  Nothing here computes env semantics on the host.
+
+`blocking=True` adds the stay-on-goal blocking penalty (`get_blocking_reward`,
+:513-546) as a second HIP pass over the calls of a launch; see mapfx_primal.h for
+the planner assumption (optimal 4-connected single-robot paths).
 """
 from __future__ import annotations
 
@@ -27,7 +31,8 @@ class PrimalBatch:
     PRIMAL's world0) or `bits` [E|1, map_stride]; starts / goals [E, N, 2] (row, col)."""
 
     def __init__(self, starts, goals, grids=None, bits=None, hw=None, observation_size=10,
-                 device=None, diagonal=False, past=None):
+                 device=None, diagonal=False, past=None, blocking=False):
+        self.blocking = bool(blocking)
         self.device = torch.device(device if device is not None else "cuda")
         if self.device.type != "cuda":
             raise RuntimeError("PrimalBatch runs on a HIP device only (got %s)" % self.device)
@@ -114,6 +119,9 @@ class PrimalBatch:
                     "valid": z((E, K), torch.uint8), "obs": z((E, K, 4, s, s), torch.uint8),
                     "vec": z((E, K, 3), torch.float64)}
         self._out = _abi.QOut(err=ptr(self.err), **{k: ptr(self.out[k]) for k in _OUT_KEYS})
+        if self.blocking:
+            self.out["blocking"] = z((E, K), torch.uint8)
+            self.out["n_blocking"] = z((E, K), torch.int32)
         self._K = K
 
     def act(self, agent_ids, actions, events=None):
@@ -121,7 +129,9 @@ class PrimalBatch:
         agent_ids (1-based) / actions: [E, K] ints.  Returns the output dict,
         each entry [E, K, ...] (buffers reused by the next call with the same K).
         events: optional (start, stop) torch.cuda.Event pair recorded at the
-        kernel's own begin / end (mapfx_primal_act_timed)."""
+        kernel's own begin / end (mapfx_primal_act_timed).  With blocking=True the
+        blocking pass follows on the same stream (outside the events): "reward"
+        carries the term, and the dict has "blocking" / "n_blocking" [E, K]."""
         ids = torch.as_tensor(agent_ids, device=self.device).to(torch.int32).contiguous()
         acts = torch.as_tensor(actions, device=self.device).to(torch.int32).contiguous()
         if ids.ndim != 2 or ids.shape[0] != self.E or acts.shape != ids.shape:
@@ -141,7 +151,27 @@ class PrimalBatch:
                                                  events[1].cuda_event,
                                                  torch.cuda.current_stream().cuda_stream),
                       "mapfx_primal_act_timed")
+            if self.blocking:
+                o = self.out
+                check(lib.mapfx_primal_blocking(self._h, ctypes.byref(self._state), ptr(ids), ptr(acts), K,
+                                                ptr(o["valid"]), ptr(o["on_goal"]), ptr(o["reward"]),
+                                                ptr(o["blocking"]), ptr(o["n_blocking"]),
+                                                torch.cuda.current_stream().cuda_stream),
+                      "mapfx_primal_blocking")
         return self.out
+
+    def blocking_count(self, agent_ids):
+        """num_blocking of `get_blocking_reward(agent_ids[e])` (:513-546) in every world
+        as it stands: [E] int32.  agent_ids (1-based): [E] ints."""
+        ids = torch.as_tensor(agent_ids, device=self.device).to(torch.int32).contiguous()
+        if ids.shape != (self.E,):
+            raise AssertionError("agent_ids must be [%d]" % self.E)
+        counts = torch.zeros((self.E,), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(lib.mapfx_primal_blocking_count(self._h, ctypes.byref(self._state), ptr(ids),
+                                                  ptr(counts), torch.cuda.current_stream().cuda_stream),
+                  "mapfx_primal_blocking_count")
+        return counts
 
     def check_err(self):
         e = int(self.err.item())
@@ -161,7 +191,8 @@ class MAPFEnv:
 
     def __init__(self, num_agents=1, observation_size=10, world0=None, goals0=None,
                  DIAGONAL_MOVEMENT=False, SIZE=(10, 40), PROB=(0, .5), FULL_HELP=False,
-                 blank_world=False, device=None):
+                 blank_world=False, device=None, blocking=False):
+        self.blocking = bool(blocking)
         self.DIAGONAL_MOVEMENT = bool(DIAGONAL_MOVEMENT)
         self.n_actions = 9 if self.DIAGONAL_MOVEMENT else 5
         self.num_agents = int(num_agents)
@@ -187,7 +218,7 @@ class MAPFEnv:
         self._grid = np.where(world0 < 0, -1, 0).astype(np.int8)
         self.batch = PrimalBatch([starts], [goals], grids=self._grid,
                                  observation_size=self.observation_size, device=self._device,
-                                 diagonal=self.DIAGONAL_MOVEMENT)
+                                 diagonal=self.DIAGONAL_MOVEMENT, blocking=self.blocking)
         self.finished = False
         self.fresh = True
         self.individual_rewards = [0 for _ in range(self.num_agents)]
@@ -199,6 +230,11 @@ class MAPFEnv:
         mask = int(o["next_mask"][0, 0].item())  # the valid moves with no previous action
         return ([a for a in range(self.n_actions) if (mask >> a) & 1],
                 bool(o["on_goal"][0, 0].item()), False)
+
+    def get_blocking_reward(self, agent_id):
+        """:513-546 -> num_blocking * BLOCKING_COST of the world as it stands."""
+        assert agent_id in range(1, self.num_agents + 1)
+        return int(self.batch.blocking_count([agent_id])[0].item()) * -1.0
 
     def getObstacleMap(self):
         return (self._grid == -1).astype(int)
@@ -225,5 +261,6 @@ class MAPFEnv:
         self.finished |= done
         next_actions = [a for a in range(self.n_actions) if (mask >> a) & 1]
         state = ([obs[i] for i in range(4)], vec)
-        return (state, reward, done, next_actions, bool(o["on_goal"][0, 0].item()), False,
+        blocking = bool(o["blocking"][0, 0].item()) if self.blocking else False
+        return (state, reward, done, next_actions, bool(o["on_goal"][0, 0].item()), blocking,
                 bool(o["valid"][0, 0].item()))
