@@ -10,6 +10,10 @@
  *                                                           per world, in order)
  *     State.moveAgent :103-135, reward table :579-596, _observe :343-386,
  *     State.done :159-166, _listNextValidActions :639-667
+ *   MAPFEnv._observe(agent_id)                :343-386      mapfx_primal_observe (Q queries
+ *   MAPFEnv._listNextValidActions(agent_id,   :639-667      per world, any agents, the
+ *                                 prev_action)              worlds are not changed)
+ *   MAPFEnv._complete()                       :404-405
  *
  * Actions: 0 stay, 1 (0,+1), 2 (+1,0), 3 (0,-1), 4 (-1,0) (dirDict, :28); with
  * cfg.diagonal (DIAGONAL_MOVEMENT, :175) also 5 (1,1), 6 (1,-1), 7 (-1,-1), 8 (-1,1):
@@ -92,6 +96,25 @@ int mapfx_primal_act(mapfx_primal_t* h, const mapfx_primal_state* st, const int3
 int mapfx_primal_act_timed(mapfx_primal_t* h, const mapfx_primal_state* st, const int32_t* agent_ids,
                            const int32_t* actions, int32_t K, const mapfx_primal_out* out,
                            void* start_event, void* stop_event, void* stream);
+
+/* _observe (:343-386), _listNextValidActions (:639-667), on_goal (:633) and State.done
+ * (:159-166) of the worlds AS THEY STAND.  Nothing in `st` is written (pos, past).
+ * Query q of world e asks about agent agent_ids[e][q] (1-based) with previous action
+ * prev_actions[e][q].  agent_ids NULL: Q must equal N and query q is agent q + 1.
+ * prev_actions NULL: 0 for every query (opposite_actions[0] removes nothing).
+ * Outputs at [e][q] of out->obs, vec, next_mask (u8, or u16 with cfg.diagonal), on_goal,
+ * done (the same value for every q of a world); out->reward and out->valid are ignored
+ * and never written; any output pointer may be NULL.  out->obs must be 4-byte aligned.
+ * MAPFX_EINVAL before any launch: NULL handle or state, Q < 0, agent_ids NULL with
+ * Q != N, a diagonal handle without st->past.  Q == 0 or E == 0: OK, no launch.
+ * A bad query (an id outside 1..N, a prev_action outside 0..nact-1) sets *out->err to
+ * 1 + its world (the first report wins, as in mapfx_primal_act) and writes none of its
+ * own output elements.  Unlike mapfx_primal_act, where a bad call stops its world
+ * (later calls depend on it), queries do not depend on each other: every other query,
+ * those of the same world included, still produces its result. */
+int mapfx_primal_observe(mapfx_primal_t* h, const mapfx_primal_state* st,
+                         const int32_t* agent_ids, const int32_t* prev_actions,
+                         int32_t Q, const mapfx_primal_out* out, void* stream);
 
 /* get_blocking_reward(agent_ids[e]) (:513-546) of every world at st->pos as it stands
  * (the agent need not be on its goal, as in the reference): counts[e] = num_blocking

@@ -723,6 +723,8 @@ struct mapfx_primal_t {
   double* pow_lut;
   int lds;
   int blocking_flat;  // MAPFX_PRIMAL_BLOCKING=flat: the flat-set blocking kernel at every shape
+  int observe_pin;    // MAPFX_PRIMAL_OBSERVE=waves / lanes: 1 the wave-per-query observe kernel at
+                      // every shape, 2 the lane-per-query kernel wherever its LDS fits
 };
 
 namespace {
@@ -1118,6 +1120,378 @@ int launch_blocking(mapfx_primal_t* h, const BArgs& a, void* stream) {
   return check_hip(hipGetLastError(), "primal_blocking_kernel launch");
 }
 
+// ---------------------------------------------------------------------------
+// primal_observe_kernel<S, DIAG>: _observe (:343-386), _listNextValidActions (:639-667),
+// on_goal (:633) and State.done (:159-166) of the worlds as they stand; nothing of the
+// state is written.  Queries do not depend on each other: one wave per (world, query),
+// a.nw waves per workgroup, a.chunks workgroups per world.
+//
+// A workgroup stages its world once -- the obstacle bitmap as it lies in memory (H * W
+// bits, at most 2 KB: no padded byte map, the queries touch only Q * s * s cells) and the
+// agents' {row, col, goal row, goal col} (DIAG: past) records -- and each wave builds its
+// query's [4][s][s] record in its own LDS slab:
+//   cells over lanes: obstacle plane from the bitmap (outside the grid = 1, :356-359),
+//     own goal plane, the other two planes cleared;
+//   agents over lanes: an agent inside the window stamps poss_map, and (unless it is the
+//     queried agent) its goal, clamped into the window, into goals_map (:369-378); the
+//     same pass finds the neighbours that refuse a move (a robot on the target, DIAG: a
+//     crossing of (past, present), :77-99) and counts the agents on their goals;
+//   the record is 4 s^2 bytes at offset (e Q + q) 4 s^2, a whole number of dwords for
+//     every s: it leaves the slab as s^2 coalesced dword stores, odd s included.
+// A bad query (id outside 1..N, prev_action outside 0..nact-1) reports 1 + world in err
+// (first report wins, as in primal_act_kernel) and writes nothing; its wave ends, the
+// other queries of the world are other waves.
+// ---------------------------------------------------------------------------
+struct OArgs {
+  const int32_t* pos;
+  const int32_t* goal;
+  const uint8_t* bits;
+  const int32_t* past;
+  const int32_t* ids;    // NULL: query q is agent q + 1
+  const int32_t* prev;   // NULL: previous action 0
+  int Q, chunks, nw;     // queries per world, workgroups per world, waves per workgroup
+  int wmax, w_ag, w_past;  // packed kernel: worlds a wave can span, offsets inside a staged world
+  int off_ag, off_past, off_rec, rec_bytes;  // LDS regions; a wave's slab is rec_bytes
+  uint8_t* obs;
+  double* vec;
+  uint8_t* next_mask;
+  uint8_t* on_goal;
+  uint8_t* done;
+  int32_t* err;
+  const double* pow_lut;
+};
+
+template <int S_, bool DIAG>
+__global__ void __launch_bounds__(1024) primal_observe_kernel(QGeo g, OArgs a) {
+  extern __shared__ __align__(16) unsigned char lds[];
+  constexpr int NDIR = DIAG ? 8 : 4;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nthr = a.nw * 64;
+  const int e = (int)(blockIdx.x / (unsigned)a.chunks), ch = (int)(blockIdx.x - (unsigned)e * (unsigned)a.chunks);
+  const int N = g.N, H = g.H, W = g.W;
+  const int s = S_ ? S_ : g.s, ss = s * s, h2 = s / 2;
+  const uint32_t* bm = (const uint32_t*)lds;             // the world's obstacle bitmap
+  const int4* agL = (const int4*)(lds + a.off_ag);       // [N] {row, col, goal row, goal col}
+  const int2* pastL = (const int2*)(lds + a.off_past);   // [N] agents_past (DIAG)
+  uint8_t* rec = lds + a.off_rec + wv * a.rec_bytes;     // this wave's [4][s][s] record
+
+  // ---- the world, once per workgroup ----
+  {
+    const uint32_t* src = (const uint32_t*)(a.bits + (g.map_shared ? 0 : (long long)e * g.map_stride));
+    for (int w = tid; w < g.bits_words; w += nthr) ((uint32_t*)lds)[w] = src[w];
+    for (int b = tid; b < N; b += nthr) {
+      const long long i = (long long)e * N + b;
+      const int2 p = ((const int2*)a.pos)[i], q = ((const int2*)a.goal)[i];
+      ((int4*)(lds + a.off_ag))[b] = make_int4(p.x, p.y, q.x, q.y);
+      if constexpr (DIAG) ((int2*)(lds + a.off_past))[b] = ((const int2*)a.past)[i];
+    }
+  }
+  __syncthreads();
+
+  const int q = ch * a.nw + wv;
+  if (q >= a.Q) return;  // (no workgroup barrier below)
+  const long long oi = (long long)e * a.Q + q;
+  const int aid = (a.ids ? a.ids[oi] : q + 1) - 1, prev = a.prev ? a.prev[oi] : 0;
+  if ((unsigned)aid >= (unsigned)N || (unsigned)prev >= (unsigned)g.nact) {  // the reference asserts / KeyErrors
+    if (lane == 0 && a.err) atomicCAS(a.err, 0, e + 1);
+    return;
+  }
+  const int4 A = agL[aid];
+  const int tr = A.x - h2, tc = A.y - h2;  // top_left (:345-346)
+
+  // ---- cells over lanes: obstacle and own-goal planes, poss_map / goals_map cleared ----
+  if (a.obs) {
+    for (int i = lane; i < ss; i += 64) {
+      const int y = S_ ? i / s : fdiv(i, g.m_s), x = i - y * s;
+      const int r = tr + y, c = tc + x;
+      const bool in = r >= 0 && r < H && c >= 0 && c < W;
+      const int idx = in ? r * W + c : 0;
+      const bool wall = !in || ((bm[idx >> 5] >> (idx & 31)) & 1u);
+      rec[i] = 0;
+      rec[ss + i] = (r == A.z && c == A.w) ? 1 : 0;  // (:366-368; the goal is inside the grid)
+      rec[2 * ss + i] = 0;
+      rec[3 * ss + i] = wall ? 1 : 0;                // (:356-362)
+    }
+  }
+  // ---- _listNextValidActions (:639-667): lane d probes action d for bounds and wall ----
+  bool ok = false;
+  if (lane >= 1 && lane <= NDIR) {
+    const int nx = A.x + dir_r(lane), ny = A.y + dir_c(lane);
+    const bool in = nx >= 0 && nx < H && ny >= 0 && ny < W;
+    const int idx = in ? nx * W + ny : 0;
+    ok = in && !((bm[idx >> 5] >> (idx & 31)) & 1u);
+  }
+  uint32_t mask = 1u | ((uint32_t)__ballot(ok) & (NDIR == 8 ? 0x1FEu : 0x1Eu));
+  wave_fence();
+  // ---- agents over lanes ----
+  uint32_t refuse = 0;  // directions with a robot on the target or (DIAG) a diagonal crossing
+  int ngoal = 0;
+  for (int b0 = 0; b0 < N; b0 += 64) {
+    const int b = b0 + lane;
+    bool og = false;
+    if (b < N) {
+      const int4 B = agL[b];
+      og = B.x == B.z && B.y == B.w;
+      const int wy = B.x - tr, wx = B.y - tc;
+      if (a.obs && wy >= 0 && wy < s && wx >= 0 && wx < s) {
+        rec[wy * s + wx] = 1;  // poss_map: the agent itself and the others (:363-372)
+        if (b != aid) {        // a visible agent's goal, clamped into view (:374-378)
+          const int mr = max(tr, min(tr + s - 1, B.z)), mc = max(tc, min(tc + s - 1, B.w));
+          rec[2 * ss + (mr - tr) * s + (mc - tc)] = 1;
+        }
+      }
+      if (b != aid) {
+        const int rx = B.x - A.x, ry = B.y - A.y;  // a robot on a neighbouring cell
+        if (rx >= -1 && rx <= 1 && ry >= -1 && ry <= 1)
+          refuse |= 1u << (uint32_t)((ACT_OF >> (4 * ((rx + 1) * 3 + ry + 1))) & 0xFu);
+        if constexpr (DIAG) {  // equal midpoints of (past, present) and (position, target)
+          const int2 pp = pastL[b];
+          const int sx = pp.x + B.x - 2 * A.x, sy = pp.y + B.y - 2 * A.y;
+          if (sx >= -1 && sx <= 1 && sy >= -1 && sy <= 1)
+            refuse |= 1u << (uint32_t)((ACT_OF >> (4 * ((sx + 1) * 3 + sy + 1))) & 0xFu);
+        }
+      }
+    }
+    ngoal += __popcll(__ballot(og));
+  }
+#pragma unroll
+  for (int d = 1; d <= NDIR; ++d)
+    if (__ballot((refuse >> d) & 1u)) mask &= ~(1u << d);
+  const int opp = opposite(prev);
+  if (opp > 0) mask &= ~(1u << opp);
+  wave_fence();
+  // ---- the record: s^2 dwords, coalesced ----
+  if (a.obs) {
+    uint32_t* o32 = (uint32_t*)(a.obs + oi * 4 * ss);
+    const uint32_t* r32 = (const uint32_t*)rec;
+    for (int m = lane; m < ss; m += 64) o32[m] = r32[m];
+  }
+  if (lane == 0) {
+    if (a.done) a.done[oi] = ngoal == N ? 1 : 0;                        // world.done() (:159-166)
+    if (a.on_goal) a.on_goal[oi] = (A.x == A.z && A.y == A.w) ? 1 : 0;  // (:633)
+    if (a.next_mask) {
+      if constexpr (DIAG) ((uint16_t*)a.next_mask)[oi] = (uint16_t)mask;
+      else a.next_mask[oi] = (uint8_t)mask;
+    }
+    if (a.vec) {  // :380-386, magnitude from the host libm pow LUT
+      const int dX = A.z - A.x, dY = A.w - A.y;
+      const double mag = a.pow_lut[dX * dX + dY * dY];
+      double vx = (double)dX, vy = (double)dY;
+      if (mag != 0.0) {
+        vx = vx / mag;
+        vy = vy / mag;
+      }
+      double* v = a.vec + oi * 3;
+      v[0] = vx;
+      v[1] = vy;
+      v[2] = mag;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// primal_observe_packed_kernel<DIAG>: the same answers with one LANE per query, the
+// second half of primal_seq_kernel's idea (its phase B) without a move chain in front.
+//
+// A wave-per-query costs a few hundred wave instructions per query whatever the lanes
+// do, and 65,536 queries of the bench shape then are VALU-issue bound far above what
+// the record bytes cost.  Here wave w answers the 64 consecutive queries 64 w .. 64 w +
+// 63 of the flat [E][Q] order: it stages the (at most a.wmax) worlds those queries belong
+// to -- bitmap and agent records, as above -- and every lane builds its query's four
+// planes as ONE 4 s^2-bit string (plane p at bits p s^2; the obstacle rows are s-bit
+// extracts of the bitmap, agents and clamped goals single bits).  The 64 strings are
+// packed back to back in LDS, so bit i of the packed string is byte i of the wave's
+// contiguous run of records: the wave expands 32 bits to two 16-byte stores per lane.
+// Strings of neighbouring lanes share a dword when 4 s^2 is no multiple of 32, so bits are
+// set with LDS atomic ORs.  A wave with a bad query expands dword by dword and leaves the
+// bad query's bytes alone.
+// ---------------------------------------------------------------------------
+__device__ inline uint32_t lowmask(int n) { return n >= 32 ? ~0u : (1u << n) - 1u; }
+__device__ inline uint32_t nibble_bytes(uint32_t v) { return ((v & 15u) * 0x00204081u) & 0x01010101u; }
+
+template <bool DIAG>
+__global__ void __launch_bounds__(64) primal_observe_packed_kernel(QGeo g, OArgs a) {
+  extern __shared__ __align__(16) unsigned char lds[];
+  constexpr int NDIR = DIAG ? 8 : 4;
+  const int lane = threadIdx.x;
+  const int N = g.N, H = g.H, W = g.W, s = g.s, ss = s * s, h2 = s / 2, Q = a.Q;
+  const long long total = (long long)g.E * Q, f0 = (long long)blockIdx.x * 64, f = f0 + lane;
+  const int nq = (int)min(64ll, total - f0);             // queries of this wave
+  const int e_lo = (int)(f0 / Q), e_hi = (int)((f0 + nq - 1) / Q);  // its worlds (at most a.wmax)
+  uint32_t* str = (uint32_t*)lds;                          // [8 s^2 + 1] the packed strings
+  unsigned char* wbase = lds + a.off_ag;                   // staged worlds, a.rec_bytes each:
+  const int o_ag = a.w_ag, o_past = a.w_past;            // ... bitmap, agent records, past
+
+  for (int i = lane; i < 8 * ss + 1; i += 64) str[i] = 0u;
+  // staging, flat over (world, item) with the loads of four rounds in flight together
+  // (a loop over the worlds would pay one global round trip per world)
+  {
+    const int per = g.bits_words + N, T = (e_hi - e_lo + 1) * per;
+    for (int i0 = 0; i0 < T; i0 += 256) {
+      uint32_t bw[4];
+      int2 P[4], G[4], PP[4];
+      int wo[4], item[4];  // the item's world (LDS byte offset) and index; item < 0: none
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const int idx = i0 + lane + 64 * t;
+        item[t] = -1, wo[t] = 0;
+        if (idx < T) {
+          const int wl = (int)((unsigned)idx / (unsigned)per), it = idx - wl * per;
+          const long long ew = e_lo + wl;
+          item[t] = it, wo[t] = wl * a.rec_bytes;
+          if (it < g.bits_words) {
+            bw[t] = ((const uint32_t*)(a.bits + (g.map_shared ? 0 : ew * g.map_stride)))[it];
+          } else {
+            const long long i = ew * N + (it - g.bits_words);
+            P[t] = ((const int2*)a.pos)[i];
+            G[t] = ((const int2*)a.goal)[i];
+            if constexpr (DIAG) PP[t] = ((const int2*)a.past)[i];
+          }
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        if (item[t] < 0) continue;
+        if (item[t] < g.bits_words) {
+          *(uint32_t*)(wbase + wo[t] + 4 * item[t]) = bw[t];
+        } else {
+          const int b = item[t] - g.bits_words;
+          *(int4*)(wbase + wo[t] + a.w_ag + 16 * b) = make_int4(P[t].x, P[t].y, G[t].x, G[t].y);
+          if constexpr (DIAG) *(int2*)(wbase + wo[t] + a.w_past + 8 * b) = PP[t];
+        }
+      }
+    }
+  }
+  const bool live = lane < nq;
+  int aid = 0, prev = 0, e = e_lo;
+  if (live) {
+    e = (int)(f / Q);
+    aid = (a.ids ? a.ids[f] : (int)(f - (long long)e * Q) + 1) - 1;
+    prev = a.prev ? a.prev[f] : 0;
+  }
+  const bool okq = live && (unsigned)aid < (unsigned)N && (unsigned)prev < (unsigned)g.nact;
+  if (live && !okq && a.err) atomicCAS(a.err, 0, e + 1);  // the reference asserts / KeyErrors
+  const uint64_t okm = __ballot(okq);
+  wave_fence();
+  if (okq) {
+    const unsigned char* wr = wbase + (e - e_lo) * a.rec_bytes;
+    const uint32_t* bm = (const uint32_t*)wr;
+    const int4* agL = (const int4*)(wr + o_ag);
+    const int2* pastL = (const int2*)(wr + o_past);
+    const int4 A = agL[aid];
+    const int tr = A.x - h2, tc = A.y - h2;  // top_left (:345-346)
+    const uint32_t sb = (uint32_t)lane * 4u * (uint32_t)ss;  // first bit of this lane's string
+    if (a.obs) {
+      // obstacle plane (:356-362): row y is the bitmap's bits of columns c0 .. c0 + n - 1
+      // at window columns sh .. sh + n - 1, ones outside the grid
+      const int c0 = max(tc, 0), n = min(tc + s, W) - c0, sh = c0 - tc;  // (n >= 1: the agent's column)
+      const uint32_t full = lowmask(s), inside = lowmask(n) << sh;
+      for (int y = 0; y < s; ++y) {
+        const int r = tr + y;
+        uint32_t row = full;
+        if (r >= 0 && r < H) {
+          const int i0 = r * W + c0, w0 = i0 >> 5;
+          const uint64_t two = (uint64_t)bm[w0] | ((uint64_t)bm[min(w0 + 1, g.bits_words - 1)] << 32);
+          row = (full & ~inside) | (((uint32_t)(two >> (i0 & 31)) << sh) & inside);
+        }
+        const uint32_t B = sb + 3u * ss + (uint32_t)(y * s), o = B & 31u;
+        atomicOr(&str[B >> 5], row << o);
+        if (o + (uint32_t)s > 32u) atomicOr(&str[(B >> 5) + 1], row >> (32u - o));
+      }
+      const int gy = A.z - tr, gx = A.w - tc;  // own goal (:366-368)
+      if (gy >= 0 && gy < s && gx >= 0 && gx < s) {
+        const uint32_t B = sb + ss + (uint32_t)(gy * s + gx);
+        atomicOr(&str[B >> 5], 1u << (B & 31u));
+      }
+    }
+    // _listNextValidActions (:639-667): bounds and walls, then robots and crossings
+    uint32_t mask = 1u, refuse = 0u;
+#pragma unroll
+    for (int d = 1; d <= NDIR; ++d) {
+      const int nx = A.x + dir_r(d), ny = A.y + dir_c(d);
+      const bool in = nx >= 0 && nx < H && ny >= 0 && ny < W;
+      const int idx = in ? nx * W + ny : 0;
+      if (in && !((bm[idx >> 5] >> (idx & 31)) & 1u)) mask |= 1u << d;
+    }
+    int ngoal = 0;
+    for (int b = 0; b < N; ++b) {
+      const int4 B4 = agL[b];
+      ngoal += (B4.x == B4.z && B4.y == B4.w) ? 1 : 0;
+      const int wy = B4.x - tr, wx = B4.y - tc;
+      if (a.obs && wy >= 0 && wy < s && wx >= 0 && wx < s) {
+        const uint32_t B = sb + (uint32_t)(wy * s + wx);  // poss_map (:363-372)
+        atomicOr(&str[B >> 5], 1u << (B & 31u));
+        if (b != aid) {  // a visible agent's goal, clamped into view (:374-378)
+          const int mr = max(tr, min(tr + s - 1, B4.z)), mc = max(tc, min(tc + s - 1, B4.w));
+          const uint32_t G = sb + 2u * ss + (uint32_t)((mr - tr) * s + (mc - tc));
+          atomicOr(&str[G >> 5], 1u << (G & 31u));
+        }
+      }
+      if (b != aid) {
+        const int rx = B4.x - A.x, ry = B4.y - A.y;  // a robot on a neighbouring cell
+        if (rx >= -1 && rx <= 1 && ry >= -1 && ry <= 1)
+          refuse |= 1u << (uint32_t)((ACT_OF >> (4 * ((rx + 1) * 3 + ry + 1))) & 0xFu);
+        if constexpr (DIAG) {  // equal midpoints of (past, present) and (position, target)
+          const int2 pp = pastL[b];
+          const int sx = pp.x + B4.x - 2 * A.x, sy = pp.y + B4.y - 2 * A.y;
+          if (sx >= -1 && sx <= 1 && sy >= -1 && sy <= 1)
+            refuse |= 1u << (uint32_t)((ACT_OF >> (4 * ((sx + 1) * 3 + sy + 1))) & 0xFu);
+        }
+      }
+    }
+    mask &= ~(refuse & 0x1FEu);
+    const int opp = opposite(prev);
+    if (opp > 0) mask &= ~(1u << opp);
+    if (a.done) a.done[f] = ngoal == N ? 1 : 0;                        // world.done() (:159-166)
+    if (a.on_goal) a.on_goal[f] = (A.x == A.z && A.y == A.w) ? 1 : 0;  // (:633)
+    if (a.next_mask) {
+      if constexpr (DIAG) ((uint16_t*)a.next_mask)[f] = (uint16_t)mask;
+      else a.next_mask[f] = (uint8_t)mask;
+    }
+    if (a.vec) {  // :380-386, magnitude from the host libm pow LUT
+      const int dX = A.z - A.x, dY = A.w - A.y;
+      const double mag = a.pow_lut[dX * dX + dY * dY];
+      double vx = (double)dX, vy = (double)dY;
+      if (mag != 0.0) {
+        vx = vx / mag;
+        vy = vy / mag;
+      }
+      double* v = a.vec + f * 3;
+      v[0] = vx;
+      v[1] = vy;
+      v[2] = mag;
+    }
+  }
+  if (!a.obs) return;
+  wave_fence();
+  // ---- the wave's records: nq * s^2 dwords, dword d = bits 4 d .. 4 d + 3 ----
+  const int nd = nq * ss;
+  int d0 = 0;  // dwords below d0 leave as 16-byte stores
+  if (okm == (nq == 64 ? ~0ull : (1ull << nq) - 1ull)) {
+    const int nch = nd >> 2;
+    uint4* obase = (uint4*)(a.obs + f0 * 4 * ss);  // (16-byte aligned: the host checks a.obs)
+    for (int i = lane; 2 * i < nch; i += 64) {
+      const uint32_t b = str[i];
+      uint4 v0, v1;
+      v0.x = nibble_bytes(b), v0.y = nibble_bytes(b >> 4), v0.z = nibble_bytes(b >> 8), v0.w = nibble_bytes(b >> 12);
+      v1.x = nibble_bytes(b >> 16), v1.y = nibble_bytes(b >> 20), v1.z = nibble_bytes(b >> 24), v1.w = nibble_bytes(b >> 28);
+      obase[2 * i] = v0;
+      if (2 * i + 1 < nch) obase[2 * i + 1] = v1;
+    }
+    d0 = nch << 2;
+  }
+  uint32_t* o32 = (uint32_t*)(a.obs + f0 * 4 * ss);
+  for (int d = d0 + lane; d < nd; d += 64) {
+    const int owner = fdiv(d, g.m_ss);
+    if ((okm >> owner) & 1ull) o32[d] = nibble_bytes(str[d >> 3] >> (4 * (d & 7)));
+  }
+}
+
+using PrimalOFn = void (*)(QGeo, OArgs);
+PrimalOFn pick_observe(const QGeo& g) {
+  if (g.s == 10) return g.diag ? primal_observe_kernel<10, true> : primal_observe_kernel<10, false>;
+  return g.diag ? primal_observe_kernel<0, true> : primal_observe_kernel<0, false>;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1189,6 +1563,8 @@ int mapfx_primal_create(const mapfx_primal_cfg* cfg, mapfx_primal_t** out) {
   {
     const char* bp = getenv("MAPFX_PRIMAL_BLOCKING");
     h->blocking_flat = bp && strcmp(bp, "flat") == 0;
+    const char* op = getenv("MAPFX_PRIMAL_OBSERVE");
+    h->observe_pin = op && strcmp(op, "waves") == 0 ? 1 : op && strcmp(op, "lanes") == 0 ? 2 : 0;
   }
   if (h->lds > 64 * 1024) {
     const hipError_t e = hipFuncSetAttribute((const void*)pick_primal(g),
@@ -1275,6 +1651,80 @@ int mapfx_primal_act_timed(mapfx_primal_t* h, const mapfx_primal_state* st, cons
 int mapfx_primal_act(mapfx_primal_t* h, const mapfx_primal_state* st, const int32_t* agent_ids,
                      const int32_t* actions, int32_t K, const mapfx_primal_out* out, void* stream) {
   return mapfx_primal_act_timed(h, st, agent_ids, actions, K, out, nullptr, nullptr, stream);
+}
+
+int mapfx_primal_observe(mapfx_primal_t* h, const mapfx_primal_state* st, const int32_t* agent_ids,
+                         const int32_t* prev_actions, int32_t Q, const mapfx_primal_out* out, void* stream) {
+  if (!h) return perr(MAPFX_EINVAL, "NULL handle");
+  if (!st || !st->pos || !st->goal || !st->map_bits) return perr(MAPFX_EINVAL, "bad state");
+  const QGeo& g = h->geo;
+  if (g.diag && !st->past) return perr(MAPFX_EINVAL, "diagonal movement needs state.past");
+  if (Q < 0) return perr(MAPFX_EINVAL, "Q < 0");
+  if (!agent_ids && Q != g.N) return perr(MAPFX_EINVAL, "agent_ids NULL asks for every agent: Q must equal n_agents");
+  if (out && ((uintptr_t)out->obs & 3u)) return perr(MAPFX_EINVAL, "out->obs must be 4-byte aligned");
+  if (Q == 0 || g.E == 0) return MAPFX_OK;
+  OArgs a;
+  memset(&a, 0, sizeof(a));
+  a.pos = st->pos;
+  a.goal = st->goal;
+  a.bits = st->map_bits;
+  a.past = st->past;
+  a.ids = agent_ids;
+  a.prev = prev_actions;
+  a.Q = Q;
+  a.pow_lut = h->pow_lut;
+  if (out) {
+    a.obs = out->obs;
+    a.vec = out->vec;
+    a.next_mask = out->next_mask;
+    a.on_goal = out->on_goal;
+    a.done = out->done;
+    a.err = out->err;
+  }
+  // One lane per query (primal_observe_packed_kernel) where a world's staging is shared
+  // by enough of its queries -- at most 12 staged items (bitmap words + agents) per query;
+  // measured at the bench shape: 3 items per query (Q = 16) it is 2 x faster than a wave
+  // per query, 48 (Q = 1, a wave stages 64 worlds) 2 x slower -- and the worlds 64
+  // consecutive queries can belong to fit a wave's LDS next to the packed strings and
+  // the records leave as 16-byte stores; else one wave per query.  MAPFX_PRIMAL_OBSERVE
+  // = waves / lanes pins either (tests; lanes still needs the LDS to fit).
+  {
+    const int strs = r16((8 * g.s * g.s + 1) * 4);
+    a.w_ag = r16(g.bits_words * 4);
+    a.w_past = a.w_ag + 16 * g.N;
+    const int per_world = a.w_past + (g.diag ? r16(8 * g.N) : 0);
+    const long long total = (long long)g.E * Q;
+    const int wmax = (int)std::min<long long>(g.E, 63 / Q + 2);
+    const long long lds = strs + (long long)wmax * per_world;
+    const bool shared_enough = g.bits_words + g.N <= 12 * Q;
+    if (h->observe_pin != 1 && (shared_enough || h->observe_pin == 2) && lds <= 64 * 1024 &&
+        ((uintptr_t)a.obs & 15u) == 0) {
+      if ((total + 63) / 64 > 0x7FFFFFFFll) return perr(MAPFX_EINVAL, "n_envs * Q too large");
+      a.wmax = wmax;
+      a.off_ag = strs;
+      a.rec_bytes = per_world;
+      const PrimalOFn fn = g.diag ? primal_observe_packed_kernel<true> : primal_observe_packed_kernel<false>;
+      hipLaunchKernelGGL(fn, dim3((unsigned)((total + 63) / 64)), dim3(64), (int)lds, (hipStream_t)stream, g, a);
+      mapfx_note_kernel((const void*)fn);
+      return check_hip(hipGetLastError(), "primal_observe_packed_kernel launch");
+    }
+  }
+  // LDS of a workgroup: bitmap (<= 2 KB), agent records (<= 4 KB, DIAG + 2 KB), one
+  // 4 s^2-byte slab per wave (<= 4 KB): with up to 16 waves at most 72 KB, so the waves
+  // are capped to stay inside the 64 KB every kernel gets without an attribute.
+  a.off_ag = r16(g.bits_words * 4);
+  a.off_past = a.off_ag + 16 * g.N;
+  a.off_rec = a.off_past + (g.diag ? r16(8 * g.N) : 0);
+  a.rec_bytes = r16(4 * g.s * g.s);
+  const int maxw = std::min(16, (64 * 1024 - a.off_rec) / a.rec_bytes);
+  a.chunks = (Q + maxw - 1) / maxw;
+  a.nw = (Q + a.chunks - 1) / a.chunks;  // the world's queries spread evenly over its workgroups
+  if ((long long)g.E * a.chunks > 0x7FFFFFFFll) return perr(MAPFX_EINVAL, "n_envs * Q too large");
+  const int lds = a.off_rec + a.nw * a.rec_bytes;
+  const PrimalOFn fn = pick_observe(g);
+  hipLaunchKernelGGL(fn, dim3((unsigned)(g.E * a.chunks)), dim3(64 * a.nw), lds, (hipStream_t)stream, g, a);
+  mapfx_note_kernel((const void*)fn);
+  return check_hip(hipGetLastError(), "primal_observe_kernel launch");
 }
 
 int mapfx_primal_blocking_count(mapfx_primal_t* h, const mapfx_primal_state* st, const int32_t* agent_ids,

@@ -96,7 +96,8 @@ EXPORTS = ("mapfx_abi_version", "mapfx_last_error", "mapfx_build_id", "mapfx_las
            "mapfx_partial_goal_dist_elem_size",
            "mapfx_partial_goal_dist", "mapfx_partial_reset", "mapfx_partial_step",
            "mapfx_partial_observe", "mapfx_primal_create", "mapfx_primal_destroy",
-           "mapfx_primal_act", "mapfx_primal_act_timed", "mapfx_primal_blocking_count",
+           "mapfx_primal_act", "mapfx_primal_act_timed", "mapfx_primal_observe",
+           "mapfx_primal_blocking_count",
            "mapfx_primal_blocking", "mapfx_runner_begin", "mapfx_runner_actions", "mapfx_runner_post",
            "mapfx_runner_step", "mapfx_host_ring_alloc", "mapfx_host_ring_free")
 
@@ -159,6 +160,7 @@ def _load():
         "mapfx_primal_destroy": (None, [c_vp]),
         "mapfx_primal_act": (c_i32, [c_vp, P(QState), c_vp, c_vp, c_i32, P(QOut), c_vp]),
         "mapfx_primal_act_timed": (c_i32, [c_vp, P(QState), c_vp, c_vp, c_i32, P(QOut), c_vp, c_vp, c_vp]),
+        "mapfx_primal_observe": (c_i32, [c_vp, P(QState), c_vp, c_vp, c_i32, P(QOut), c_vp]),
         "mapfx_primal_blocking_count": (c_i32, [c_vp, P(QState), c_vp, c_vp, c_vp]),
         "mapfx_primal_blocking": (c_i32, [c_vp, P(QState), c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp,
                                           c_vp, c_vp]),

@@ -8,6 +8,10 @@ one `State.moveAgent` (:103-135), the reward table (:579-596), `_observe`
 in one HIP kernel.  `MAPFEnv` below is the single-world drop-in with the
 reference's call signature.  Nothing here computes env semantics on the host.
 
+`observe` is the read-only half: `_observe`, `_listNextValidActions`, on_goal and
+`_complete` of any agents of the worlds as they stand (mapfx_primal_observe), all
+queries of all worlds in one launch that writes nothing of the state.
+
 `blocking=True` adds the stay-on-goal blocking penalty (`get_blocking_reward`,
 :513-546) as a second HIP pass over the calls of a launch; see mapfx_primal.h for
 the planner assumption (optimal 4-connected single-robot paths).
@@ -86,6 +90,8 @@ class PrimalBatch:
                                   past=ptr(self.past))
         self._K = -1
         self.out = None
+        self._Q = -1
+        self.obs_out = None
 
     def _check_placement(self, starts, goals, bits):
         """Distinct in-bounds starts and goals on free cells: PRIMAL keeps agents,
@@ -160,6 +166,43 @@ class PrimalBatch:
                       "mapfx_primal_blocking")
         return self.out
 
+    def observe(self, agent_ids=None, prev_actions=None):
+        """`_observe` (:343-386), `_listNextValidActions` (:639-667), on_goal and
+        `State.done` of the worlds as they stand, for Q (agent, previous action) queries
+        per world; nothing of the worlds changes (pos, past, an earlier `act` result).
+        agent_ids (1-based) / prev_actions: [E, Q] ints; agent_ids None: every agent
+        (Q = N, query q is agent q + 1); prev_actions None: 0.  Returns a dict of
+        [E, Q, ...] tensors obs, vec, next_mask, on_goal, done (its own buffers, reused
+        by the next call with the same Q).  A bad query (id outside 1..N, prev_action
+        outside the action range) is reported by check_err(); its elements are not
+        written, every other query's are."""
+        ids = acts = None
+        if agent_ids is not None:
+            ids = torch.as_tensor(agent_ids, device=self.device).to(torch.int32).contiguous()
+            if ids.ndim != 2 or ids.shape[0] != self.E:
+                raise AssertionError("agent_ids must be [%d, Q]" % self.E)
+        if prev_actions is not None:
+            acts = torch.as_tensor(prev_actions, device=self.device).to(torch.int32).contiguous()
+            if acts.ndim != 2 or acts.shape[0] != self.E or (ids is not None and acts.shape != ids.shape):
+                raise AssertionError("prev_actions must be [%d, Q] like agent_ids" % self.E)
+        Q = int(ids.shape[1]) if ids is not None else (int(acts.shape[1]) if acts is not None else self.N)
+        if ids is None and Q != self.N:
+            raise AssertionError("without agent_ids every agent is queried: Q must be %d" % self.N)
+        if Q != self._Q:
+            E, s, dev = self.E, self.s, self.device
+            z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+            self.obs_out = {"obs": z((E, Q, 4, s, s), torch.uint8), "vec": z((E, Q, 3), torch.float64),
+                            "next_mask": z((E, Q), torch.int16 if self.diagonal else torch.uint8),
+                            "on_goal": z((E, Q), torch.uint8), "done": z((E, Q), torch.uint8)}
+            self._obs_out = _abi.QOut(err=ptr(self.err), **{k: ptr(v) for k, v in self.obs_out.items()})
+            self._Q = Q
+        with torch.cuda.device(self.device):
+            check(lib.mapfx_primal_observe(self._h, ctypes.byref(self._state), ptr(ids), ptr(acts), Q,
+                                           ctypes.byref(self._obs_out),
+                                           torch.cuda.current_stream().cuda_stream),
+                  "mapfx_primal_observe")
+        return self.obs_out
+
     def blocking_count(self, agent_ids):
         """num_blocking of `get_blocking_reward(agent_ids[e])` (:513-546) in every world
         as it stands: [E] int32.  agent_ids (1-based): [E] ints."""
@@ -226,10 +269,31 @@ class MAPFEnv:
     def _reset(self, agent_id, world0=None, goals0=None):
         """:389-402 -> (next valid actions, on_goal, False)."""
         self._set_world(world0, goals0)
-        o = self.batch.act([[agent_id]], [[0]])  # a stay call changes nothing; it reports
-        mask = int(o["next_mask"][0, 0].item())  # the valid moves with no previous action
+        o = self._query(agent_id, 0)  # a query: the new world (agents_past too) stays as set
+        mask = int(o["next_mask"][0, 0].item())
         return ([a for a in range(self.n_actions) if (mask >> a) & 1],
                 bool(o["on_goal"][0, 0].item()), False)
+
+    def _query(self, agent_id, prev_action):
+        assert agent_id in range(1, self.num_agents + 1)
+        assert prev_action in range(self.n_actions)
+        return self.batch.observe([[agent_id]], [[prev_action]])
+
+    def _observe(self, agent_id):
+        """:343-386 -> ([poss_map, goal_map, goals_map, obs_map], [dx, dy, mag])."""
+        assert (agent_id > 0)
+        o = self._query(agent_id, 0)
+        obs = o["obs"][0, 0].cpu().numpy()
+        return ([obs[i] for i in range(4)], o["vec"][0, 0].cpu().tolist())
+
+    def _listNextValidActions(self, agent_id, prev_action=0, episode=0):
+        """:639-667 -> the valid actions, ascending, without the opposite of prev_action."""
+        mask = int(self._query(agent_id, prev_action)["next_mask"][0, 0].item())
+        return [a for a in range(self.n_actions) if (mask >> a) & 1]
+
+    def _complete(self):
+        """:404-405 -> world.done()."""
+        return bool(self.batch.observe([[1]])["done"][0, 0].item())
 
     def get_blocking_reward(self, agent_id):
         """:513-546 -> num_blocking * BLOCKING_COST of the world as it stands."""
