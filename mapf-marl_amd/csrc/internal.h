@@ -51,7 +51,7 @@ typedef struct mapfx_runner_acts {
   // not fused; runner.hip runner_compact_kernel then runs after the step).  The alive
   // flags are double-buffered by step parity: `alive` is A[ts & 1] (running before this
   // step: read, never written) and `alive_prev` is A[(ts + 1) & 1] (written for every env:
-  // running after this step), so the launch's last workgroup compacts A[ts & 1] -- the
+  // running after this step), so the launch's first workgroup compacts A[ts & 1] -- the
   // stale list bs(ts + 1) -- while the env workgroups step.  It writes bs, the row map
   // cmp_bs_inv (bs_inv of the next step's parity), counts {len(bs), len(bs)}, env_steps
   // += len(bs) and, when not NULL, counts_out.

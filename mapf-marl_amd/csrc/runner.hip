@@ -264,7 +264,7 @@ int mapfx_runner_step(mapfx_partial_t* h, const mapfx_partial_state* st, const m
   mapfx_runner_acts ra;
   memset(&ra, 0, sizeof ra);
   // the post pass in the env step's write-back too (the one-wave-per-env-group kernel),
-  // and with it the compaction for the next MAC call as the launch's last workgroup:
+  // and with it the compaction for the next MAC call as the launch's first workgroup:
   // alive flags and the row map double-buffered by step parity (alive / alive_prev =
   // A[0] / A[1], bs_inv = [2][B]; A[ts & 1] = running before step ts)
   const bool fpost = mapfx_partial_fuses_post(h) != 0;
@@ -310,7 +310,7 @@ int mapfx_runner_step(mapfx_partial_t* h, const mapfx_partial_state* st, const m
   if ((rc = mapfx_partial_step_runner(h, st, actions, action_dtype, &ra, out, obs_row, rows->obs_sb,
                                       fpost ? a_in : rs->alive, stream)))
     return rc;
-  if (fpost) return MAPFX_OK;  // (the compaction ran as the launch's last workgroup)
+  if (fpost) return MAPFX_OK;  // (the compaction ran as the launch's first workgroup)
   if (!rows->obs) return mapfx_runner_post(rs, st->terminated, out, ts, counts_out, rows, stream);
   mapfx_episode_rows r2 = *rows;
   r2.obs = nullptr;

@@ -11,8 +11,9 @@ into the EpisodeBatch tensors with the runner's bookkeeping (running envs, the
 MAC's `bs`, returns, lengths, env steps) kept on the device.  No per-step host
 synchronisation: the loop-exit test reads the count of running envs from a pinned
 ring, written by the step two launches back (the reference stops one MAC call after
-the last env terminated; the calls the lag adds find no running env and record
-nothing; see `run`).
+the last env terminated; the one call the lag adds with the fused step finds no
+running env and records nothing, and `args.runner_exact_bs` makes exactly the
+reference's calls; see `run`).
 
 The EpisodeBatch is whatever `setup` is given (PyMARL passes
 components.episode_buffer.EpisodeBatch); the runner writes its
@@ -258,9 +259,13 @@ class ParallelRunner:
         step, mapfx_runner_step) that slot counts the envs running after step k - 3,
         else (the separate post / compaction kernels) after step k - 2 -- two
         iterations old either way, so no wait in the steady state.  The iterations
-        the lag adds past the reference's last MAC call find no running env (empty
-        `bs`, no action rows, nothing stepped) and write nothing; the loop also ends
-        when the batch has no row k (every env has met its episode limit by then)."""
+        the lag adds past the reference's last MAC call (one with the fused step, none
+        with the separate kernels) find no running env (a `bs` that is all padding, no
+        action rows, nothing stepped) and write nothing; the loop also ends when the
+        batch has no row k (every env has met its episode limit by then).  With
+        args.runner_exact_bs the loop waits for the count of step k - 1's compaction
+        anyway (len(bs) of MAC call k) and stops when it is 0, so the MAC is called
+        exactly as often as by the reference, with the reference's `bs`."""
         self.reset()
         self.mac.init_hidden(batch_size=self.batch_size)
         r, rs, env = self._erows, ctypes.byref(self._rs), self.env
@@ -286,6 +291,8 @@ class ParallelRunner:
             if exact_bs and k >= 1:   # len(bs) from step k - 1's compaction (one sync)
                 ev, hc, _ = self._ring[(k - 1) % _RING]
                 ev.synchronize()
+                if int(hc[0]) == 0:   # no env was running before step k - 1: the
+                    break             # reference stopped after MAC call k - 1
                 bs = self._bs[:int(hc[0])]
             actions = self.mac.select_actions(self.batch, t_ep=k, t_env=self.t_env, bs=bs,
                                               test_mode=test_mode)

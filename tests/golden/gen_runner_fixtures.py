@@ -64,6 +64,9 @@ class ScriptedMAC:
         return torch.tensor(out, dtype=torch.long, device=avail.device).view(len(idx), n_agents)
 
 
+_F8 = [(1, 4), (2, 6), (3, 2), (4, 4), (5, 1), (6, 5)]
+_F16 = [(2, 2), (2, 8), (4, 12), (5, 5), (6, 9), (7, 2), (8, 13), (9, 6), (11, 3), (12, 10),
+        (13, 7), (13, 13)]
 CASES = {
     # name: (map rows, n_agents, episode_limit, batch_size_run, runs, yaml-style rewards, instances)
     "runner_open5_n2": dict(
@@ -78,6 +81,22 @@ CASES = {
     "runner_solo4_n1": dict(
         grid=["....", "....", ".@..", "...."], n=1, limit=8, B=8, runs=2,
         inst=[([(1, 1)], [(1, 2)]), ([(3, 3)], [(2, 3)])]),
+    # the reference runner on the shapes of the GPU fast path (window 5, 5 nearest agents;
+    # 8 and 16 lanes per env, u8 and int16 goal tables).  scripted_action gives every agent
+    # of env b the same move at step t, so with every goal one free move (the same one)
+    # from its start, env b completes at the first step its moves add up to that offset:
+    # run 0 (goals one up) envs 0, 5 after 1 step and env 4 after 3; run 1 (one down) env
+    # 2 after 1 and env 3 after 2
+    "runner_fast8_n6": dict(
+        grid=["........", "..@.....", "........", ".....@..", "........", "........", "..@.....",
+              "........"], n=6, limit=10, B=6, runs=2, obs_window=5, obs_knn_agents=5,
+        inst=[(_F8, [(r - 1, c) for r, c in _F8]), (_F8, [(r + 1, c) for r, c in _F8])]),
+    # 16 x 16 = 256 cells: int16 goal tables.  Run 0 envs 0, 4, 1 complete after 1, 3, 7
+    # steps; run 1 envs 2, 3, 1 after 1, 2, 5
+    "runner_fast16_n12": dict(
+        grid=["." * 16] * 3 + ["....@@.........."] + ["." * 16] * 6 + [".........@......"]
+        + ["." * 16] * 5, n=12, limit=8, B=5, runs=2, obs_window=5, obs_knn_agents=5,
+        inst=[(_F16, [(r - 1, c) for r, c in _F16]), (_F16, [(r + 1, c) for r, c in _F16])]),
 }
 REWARDS = dict(move_reward=0, stay_reward=-0.1, stay_goal_reward=1, node_collide_reward=-2000,
                edge_collide_reward=-2000, env_collide_reward=-2000, complete_reward=1000,
@@ -123,7 +142,8 @@ def run_case(name, c, tmpdir):
     env_cls = make_env_cls(c["inst"])
     PR.env_REGISTRY["fixture_partial"] = partial(lambda env, **kw: env(**kw), env=env_cls)
     env_args = dict(REWARDS, grid_file_path=mp, agents_path=os.path.join(tmpdir, "unused-"),
-                    n_agents=c["n"], obs_window=3, obs_knn_agents=2, episode_limit=c["limit"])
+                    n_agents=c["n"], obs_window=c.get("obs_window", 3),
+                    obs_knn_agents=c.get("obs_knn_agents", 2), episode_limit=c["limit"])
     args = types.SimpleNamespace(batch_size_run=c["B"], env="fixture_partial", env_args=env_args,
                                  device="cpu", test_nepisode=c["B"], runner_log_interval=1)
     logger = _Logger()
@@ -140,7 +160,8 @@ def run_case(name, c, tmpdir):
     preprocess = {"actions": ("actions_onehot", [OneHot(out_dim=info["n_actions"])])}
     runner.setup(scheme, groups, preprocess, ScriptedMAC())
     rec = {"map": np.array(c["grid"]), "n_agents": c["n"], "limit": c["limit"], "B": c["B"],
-           "runs": c["runs"], "obs_window": 3, "obs_knn_agents": 2,
+           "runs": c["runs"], "obs_window": c.get("obs_window", 3),
+           "obs_knn_agents": c.get("obs_knn_agents", 2),
            "inst_starts": np.array([i[0] for i in c["inst"]], np.int32),
            "inst_goals": np.array([i[1] for i in c["inst"]], np.int32)}
     for r in range(c["runs"]):

@@ -18,7 +18,8 @@ pytestmark = pytest.mark.gpu
 REWARDS = dict(move_reward=0, stay_reward=-0.1, stay_goal_reward=1, node_collide_reward=-2000,
                edge_collide_reward=-2000, env_collide_reward=-2000, complete_reward=1000,
                complete_fac=1.5, gamma=0.99)
-CASES = ["runner_open5_n2", "runner_wall6_n3", "runner_solo4_n1"]
+CASES = ["runner_open5_n2", "runner_wall6_n3", "runner_solo4_n1", "runner_fast8_n6",
+         "runner_fast16_n12"]
 
 
 def scripted_action(b, t, n, avail_row):
