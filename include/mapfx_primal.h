@@ -136,6 +136,52 @@ int mapfx_primal_blocking(mapfx_primal_t* h, const mapfx_primal_state* st,
                           const uint8_t* valid, const uint8_t* on_goal,
                           double* reward, uint8_t* blocking, int32_t* counts, void* stream);
 
+/* MAPFEnv._setWorld (:248-341) on the device: a new episode for every world, or for the
+ * worlds with mask[e] != 0, in one launch and in place -- a random square world, the
+ * agents on random free cells, each agent's goal on a random cell of the connected
+ * region it stands in (so every episode is solvable).  The distribution is the
+ * reference's; the draws are this library's own counter-based splitmix64 streams
+ * (mapfx/rng.py), not numpy's, keyed by the world's GLOBAL id gid = env_offset + e and
+ * its episode counter ep = episode[e], so a world does not depend on how worlds are
+ * sharded over handles:
+ *   key(stream, idx) = splitmix64(seed ^ gid*K_ENV ^ ep*K_T ^ idx*K_CELL ^ stream*K_STREAM)
+ *   draw32 = key >> 32;  pick(d, n) = (d * n) >> 32;  ties between cells: row-major.
+ *   1. k = key(WORLD, 0): side = side_lut[k & (n_side-1)], thresh = prob_lut[(k >> 32) &
+ *      (n_prob-1)] (mapfx.maps.primal_gen_luts builds the reference's tables, :313-314).
+ *      The world is the top-left side x side corner of the H x W grid; every other cell is
+ *      an obstacle, which no output of act / observe can tell from the reference's
+ *      side x side world (out of bounds and wall are priced and masked alike).
+ *   2. cell (r, c), r, c < side, is an obstacle iff draw32(OBST + t, r*64 + c) < (thresh >> t)
+ *      (:315); t = 0, and t + 1 while fewer than N cells are free (t = 32: empty world).
+ *   3. agent a = 0..N-1 in order starts on cell pick(draw32(START, a), |F|) of F, the free
+ *      cells no earlier agent took (:320-325).
+ *   4. agent a's goal is cell pick(draw32(GOAL, a), |R|) of R, the free cells 4-connected
+ *      to its start (agents do not block, :265) without the earlier agents' goals (:327-336).
+ *   5. written: pos, goal, past = pos (diagonal handles), the bitmap, episode[e] = ep + 1.
+ * keep_map (blank_world, :281-305): steps 1-2 are skipped, the world's bitmap (shared or
+ * not) is read as it stands and only agents and goals are placed.
+ * A world with mask[e] == 0 is neither read nor written.  A bad world -- side outside
+ * 1..min(H, W), side * side < N, fewer than N free cells under keep_map -- sets *err to
+ * 1 + e (the first report wins) and none of its state is written; all others are generated.
+ * MAPFX_EINVAL before any launch: NULL handle / state / gen (or pos, goal, episode,
+ * map_bits), a map_shared handle without keep_map, a diagonal handle without st->past,
+ * table lengths that are not powers of two, H or W above 64 (the kernel holds a row in
+ * one 64-bit lane mask; PRIMAL's own range is SIZE = (10, 40); larger grids are out of
+ * scope of the generator).  E == 0: OK, no launch. */
+typedef struct mapfx_primal_gen {
+  uint64_t seed;
+  int64_t env_offset;          /* global id of world 0 */
+  const int32_t* side_lut;  int32_t n_side;   /* device, power-of-two length; unused with keep_map */
+  const uint32_t* prob_lut; int32_t n_prob;   /* device, power-of-two length; unused with keep_map */
+  int32_t* episode;            /* [E] device, read and incremented for generated worlds */
+  const uint8_t* mask;         /* [E] device or NULL */
+  uint8_t* map_bits;           /* [E][mapfx_map_stride(H, W)] written; with keep_map: [E or 1], read only */
+  int32_t keep_map;
+  int32_t* err;                /* [1] */
+} mapfx_primal_gen;
+int mapfx_primal_generate(mapfx_primal_t* h, const mapfx_primal_state* st /* pos, goal, past written */,
+                          const mapfx_primal_gen* gen, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

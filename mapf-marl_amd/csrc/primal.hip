@@ -1492,6 +1492,237 @@ PrimalOFn pick_observe(const QGeo& g) {
   return g.diag ? primal_observe_kernel<0, true> : primal_observe_kernel<0, false>;
 }
 
+// ---------------------------------------------------------------------------
+// primal_generate_kernel: MAPFEnv._setWorld (:248-341) for every (masked-in) world of the
+// batch -- a random square world, agents on random free cells, every agent's goal on a
+// random cell of the connected region it stands in -- by the rules of mapfx_primal.h.
+//
+// One 64-lane wave per world, GEN_WAVES worlds per workgroup; the waves never meet (no
+// workgroup barrier: a wave leaves as soon as its world is masked out or bad).  Lane r
+// holds row r as a 64-bit mask, as primal_blocking_kernel<true> does:
+//   obstacles: lane r draws its own row, one counter-based draw per cell;
+//   the k-th cell of a set: a wave prefix sum of the rows' popcounts names the row, and
+//     lane c of the wave tests "bit c is set and has k' set bits below it" of that row;
+//     the sets only shrink by the cell just picked, so the prefix sum is scanned once
+//     per run of picks (the starts; the goals of one region) and then kept by decrement;
+//   regions: the flood m |= row_nbr(m) & free runs until a ballot says nothing grew, ONCE
+//     per region: a flood started at the lowest agent without a goal is the region of
+//     every agent standing in it (regions are disjoint, so those agents, served in
+//     ascending id, see exactly the goals the plain per-agent order would have placed);
+//   lane l keeps agents l, l + 64, .. (N <= 255) in registers; positions and goals leave
+//     as coalesced int2 stores, the bitmap as whole dwords built from the rows in LDS.
+// Everything is integer arithmetic; a bad world writes nothing but *err.
+// ---------------------------------------------------------------------------
+struct GArgs {
+  uint64_t seed;
+  long long env_offset;
+  const int32_t* side_lut;
+  const uint32_t* prob_lut;
+  int n_side, n_prob;
+  int32_t* episode;
+  const uint8_t* mask;
+  uint8_t* bits;
+  int keep_map;
+  int32_t* err;
+  int32_t* pos;
+  int32_t* goal;
+  int32_t* past;
+};
+
+constexpr int GEN_WAVES = 4;
+// mapfx/rng.py: K_ENV, K_T, K_CELL, K_STREAM and the generator's stream ids
+constexpr uint64_t GK_ENV = 0xD1B54A32D192ED03ull, GK_T = 0xABC98388FB8FAC03ull,
+                   GK_CELL = 0x9E6C63D0676A9A99ull, GK_STREAM = 0xF1357AEA2E62A9C5ull;
+constexpr uint32_t GS_WORLD = 0x100u, GS_OBST = 0x200u, GS_START = 0x300u, GS_GOAL = 0x400u;
+
+__device__ inline uint64_t gen_mix(uint64_t x) {  // splitmix64 (mapfx.hip)
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+__device__ inline uint64_t gen_key(uint64_t base, uint32_t stream, uint32_t idx) {
+  return gen_mix(base ^ ((uint64_t)idx * GK_CELL) ^ ((uint64_t)stream * GK_STREAM));
+}
+__device__ inline uint32_t gen_draw32(uint64_t base, uint32_t stream, uint32_t idx) {
+  return (uint32_t)(gen_key(base, stream, idx) >> 32);
+}
+
+// inclusive prefix sum over the wave
+__device__ inline int wave_scan(int v, int lane) {
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int u = __shfl_up(v, d);
+    if (lane >= d) v += u;
+  }
+  return v;
+}
+__device__ inline uint64_t readlane_u64(uint64_t v, int l) {
+  return ((uint64_t)readlane_u32((uint32_t)(v >> 32), l) << 32) | readlane_u32((uint32_t)v, l);
+}
+
+// Cell number pick(draw, |x|) of the set x (lane = row, row-major order): its (row, col),
+// the same in every lane.  inc is the inclusive prefix sum over the lanes of the rows'
+// popcounts, kept by the caller: taking one cell out of row r is `inc -= lane >= r`, so
+// a run of picks from a shrinking set costs one wave_scan, not one per pick.  x must
+// not be empty.
+__device__ inline void gen_pick_cell(uint64_t x, int inc, uint32_t draw, int lane, int& row, int& col) {
+  const int exc = inc - __popcll(x);
+  const uint32_t total = (uint32_t)__builtin_amdgcn_readlane(inc, 63);
+  const uint32_t k = (uint32_t)(((uint64_t)draw * total) >> 32);
+  const uint64_t hit = __ballot((uint32_t)exc <= k && k < (uint32_t)inc);
+  row = __builtin_amdgcn_readfirstlane((int)__ffsll((unsigned long long)hit) - 1) & 63;
+  const uint32_t kk = k - (uint32_t)__builtin_amdgcn_readlane(exc, row);
+  const uint64_t bits = readlane_u64(x, row);
+  const bool me = ((bits >> lane) & 1ull) != 0 && (uint32_t)__popcll(bits & ((1ull << lane) - 1ull)) == kk;
+  col = __builtin_amdgcn_readfirstlane((int)__ffsll((unsigned long long)__ballot(me)) - 1) & 63;
+}
+
+__global__ void __launch_bounds__(64 * GEN_WAVES) primal_generate_kernel(QGeo g, GArgs a) {
+  __shared__ uint64_t rowsL[GEN_WAVES][64];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int e = blockIdx.x * GEN_WAVES + wv;
+  if (e >= g.E) return;               // (wave-uniform, like every exit below)
+  if (a.mask && !a.mask[e]) return;   // masked out: nothing of the world is read or written
+  const int N = g.N, H = g.H, W = g.W;
+  const int ep = a.episode[e];
+  const uint64_t base = a.seed ^ ((uint64_t)(a.env_offset + e) * GK_ENV) ^ ((uint64_t)(uint32_t)ep * GK_T);
+  const long long moff = g.map_shared ? 0 : (long long)e * g.map_stride;
+  uint64_t fre = 0;  // the free cells of row `lane`
+  bool bad;
+  if (!a.keep_map) {
+    // ---- world draw (:313-314 by table) and obstacles (:315), redrawn at half the
+    //      density while fewer than N cells are free: attempt 32 is the empty world ----
+    const uint64_t k = gen_key(base, GS_WORLD, 0);
+    const int side = a.side_lut[(uint32_t)k & (uint32_t)(a.n_side - 1)];
+    const uint32_t thresh = a.prob_lut[(uint32_t)(k >> 32) & (uint32_t)(a.n_prob - 1)];
+    bad = side < 1 || side > min(H, W) || side * side < N;
+    if (!bad) {
+      const uint64_t sm = side >= 64 ? ~0ull : (1ull << side) - 1ull;
+      for (uint32_t t = 0; t <= 32u; ++t) {
+        const uint32_t th = (uint32_t)((uint64_t)thresh >> t);
+        uint64_t ob = 0;
+        if (th != 0u && lane < side)
+          for (int c = 0; c < side; ++c)
+            ob |= (uint64_t)(gen_draw32(base, GS_OBST + t, (uint32_t)(lane * 64 + c)) < th ? 1u : 0u) << c;
+        fre = lane < side ? ~ob & sm : 0ull;
+        const int nfree = __builtin_amdgcn_readlane(wave_scan(__popcll(fre), lane), 63);
+        if (nfree >= N) break;
+      }
+    }
+  } else {
+    // ---- blank_world (:281-305): the world's bitmap as it stands ----
+    if (lane < H) {
+      const uint32_t* src = (const uint32_t*)(a.bits + moff);
+      const int b0 = lane * W, wi = b0 >> 5, sh = b0 & 31, last = (b0 + W - 1) >> 5;
+      const uint64_t d0 = src[wi], d1 = wi + 1 <= last ? src[wi + 1] : 0u, d2 = wi + 2 <= last ? src[wi + 2] : 0u;
+      uint64_t v = (d0 | (d1 << 32)) >> sh;
+      if (sh) v |= d2 << (64 - sh);
+      fre = ~v & (W >= 64 ? ~0ull : (1ull << W) - 1ull);
+    }
+    bad = __builtin_amdgcn_readlane(wave_scan(__popcll(fre), lane), 63) < N;
+  }
+  if (bad) {
+    if (lane == 0 && a.err) atomicCAS(a.err, 0, e + 1);
+    return;
+  }
+  // ---- starts (:320-325): agent a on a uniform cell of the free cells still empty ----
+  int srow[4], scol[4], grow[4], gcol[4];
+  {
+    uint64_t avail = fre;
+    int inc = wave_scan(__popcll(avail), lane);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      srow[j] = scol[j] = grow[j] = gcol[j] = 0;
+      for (int i = 0; i < 64 && 64 * j + i < N; ++i) {
+        int r, c;
+        gen_pick_cell(avail, inc, gen_draw32(base, GS_START, (uint32_t)(64 * j + i)), lane, r, c);
+        if (lane == r) avail &= ~(1ull << c);
+        inc -= lane >= r ? 1 : 0;
+        if (lane == i) srow[j] = r, scol[j] = c;
+      }
+    }
+  }
+  // ---- goals (:327-336): one flood per region, its agents served in ascending id ----
+  {
+    uint64_t gtaken = 0;                  // row `lane` of the cells that hold a goal
+    uint64_t served[4] = {0ull, 0ull, 0ull, 0ull};  // agents 64 j + bit with a goal (uniform)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (64 * j >= N) break;
+      const int nj = min(64, N - 64 * j);
+      const uint64_t all = nj >= 64 ? ~0ull : (1ull << nj) - 1ull;
+      while (all & ~served[j]) {
+        const int i0 = __builtin_amdgcn_readfirstlane((int)__ffsll((unsigned long long)(all & ~served[j])) - 1);
+        const int r0 = __builtin_amdgcn_readlane(srow[j], i0), c0 = __builtin_amdgcn_readlane(scol[j], i0);
+        uint64_t m = lane == r0 ? 1ull << c0 : 0ull;
+        for (;;) {
+          const uint64_t nm = m | (row_nbr(m, lane) & fre);
+          const bool grew = nm != m;
+          m = nm;
+          if (!__ballot(grew)) break;
+        }
+        int inc = wave_scan(__popcll(m & ~gtaken), lane);  // the region's cells still without a goal
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+          if (jj < j || 64 * jj >= N) continue;
+          // agent 64 jj + lane stands in the region (an earlier agent cannot: its own
+          // flood would have served the agent this flood started from)
+          const uint64_t mr = __shfl(m, srow[jj]);
+          const bool in = 64 * jj + lane < N && ((mr >> scol[jj]) & 1ull) != 0;
+          uint64_t todo = __ballot(in) & ~served[jj];
+          served[jj] |= todo;
+          while (todo) {
+            const int i = __builtin_amdgcn_readfirstlane((int)__ffsll((unsigned long long)todo) - 1);
+            todo &= todo - 1ull;
+            int r, c;
+            gen_pick_cell(m & ~gtaken, inc, gen_draw32(base, GS_GOAL, (uint32_t)(64 * jj + i)), lane, r, c);
+            if (lane == r) gtaken |= 1ull << c;
+            inc -= lane >= r ? 1 : 0;
+            if (lane == i) grow[jj] = r, gcol[jj] = c;
+          }
+        }
+      }
+    }
+  }
+  // ---- writes: pos, goal, past = pos (:55-66), the bitmap, the episode counter ----
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int b = 64 * j + lane;
+    if (b < N) {
+      const long long i = (long long)e * N + b;
+      ((int2*)a.pos)[i] = make_int2(srow[j], scol[j]);
+      ((int2*)a.goal)[i] = make_int2(grow[j], gcol[j]);
+      if (a.past) ((int2*)a.past)[i] = make_int2(srow[j], scol[j]);
+    }
+  }
+  if (!a.keep_map) {
+    // obstacle rows -> LDS; dword w of the bitmap is bits 32 w .. 32 w + 31 of the row-major
+    // H * W bit string (rows of a W that does not divide 32 straddle dwords), 0 past its end
+    rowsL[wv][lane] = lane < H ? ~fre & (W >= 64 ? ~0ull : (1ull << W) - 1ull) : 0ull;
+    wave_fence();
+    uint32_t* dst = (uint32_t*)(a.bits + moff);
+    const int nd = (int)(g.map_stride >> 2);
+    for (int w = lane; w < nd; w += 64) {
+      uint32_t v = 0;
+      const int b0 = 32 * w;
+      if (b0 < g.hw) {
+        int r = b0 / W, c = b0 - r * W, p = 0;
+        while (p < 32 && r < H) {
+          const int take = min(W - c, 32 - p);
+          const uint32_t piece = (uint32_t)(rowsL[wv][r] >> c) & (take >= 32 ? ~0u : (1u << take) - 1u);
+          v |= piece << p;
+          p += take;
+          ++r;
+          c = 0;
+        }
+      }
+      dst[w] = v;
+    }
+  }
+  if (lane == 0) a.episode[e] = ep + 1;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1768,6 +1999,45 @@ int mapfx_primal_blocking(mapfx_primal_t* h, const mapfx_primal_state* st, const
   a.counts = counts;
   a.undo = 1;
   return launch_blocking(h, a, stream);
+}
+
+int mapfx_primal_generate(mapfx_primal_t* h, const mapfx_primal_state* st, const mapfx_primal_gen* gen,
+                          void* stream) {
+  if (!h) return perr(MAPFX_EINVAL, "NULL handle");
+  if (!st || !st->pos || !st->goal) return perr(MAPFX_EINVAL, "bad state: the generator writes pos and goal");
+  if (!gen || !gen->episode || !gen->map_bits) return perr(MAPFX_EINVAL, "NULL gen, gen->episode or gen->map_bits");
+  const QGeo& g = h->geo;
+  if (g.map_shared && !gen->keep_map)
+    return perr(MAPFX_EINVAL, "a map_shared handle generates with keep_map only (one map cannot hold E worlds)");
+  if (g.diag && !st->past) return perr(MAPFX_EINVAL, "diagonal movement needs state.past");
+  if (g.H > 64 || g.W > 64) return perr(MAPFX_EINVAL, "the generator supports H <= 64 and W <= 64");
+  if (!gen->keep_map) {
+    if (!gen->side_lut || !gen->prob_lut) return perr(MAPFX_EINVAL, "NULL side_lut / prob_lut without keep_map");
+    const auto pow2 = [](int n) { return n >= 1 && (n & (n - 1)) == 0; };
+    if (!pow2(gen->n_side) || !pow2(gen->n_prob))
+      return perr(MAPFX_EINVAL, "n_side and n_prob must be powers of two");
+  }
+  if (g.E == 0) return MAPFX_OK;
+  GArgs a;
+  memset(&a, 0, sizeof(a));
+  a.seed = gen->seed;
+  a.env_offset = gen->env_offset;
+  a.side_lut = gen->side_lut;
+  a.prob_lut = gen->prob_lut;
+  a.n_side = gen->n_side;
+  a.n_prob = gen->n_prob;
+  a.episode = gen->episode;
+  a.mask = gen->mask;
+  a.bits = gen->map_bits;
+  a.keep_map = gen->keep_map ? 1 : 0;
+  a.err = gen->err;
+  a.pos = st->pos;
+  a.goal = const_cast<int32_t*>(st->goal);
+  a.past = g.diag ? st->past : nullptr;
+  hipLaunchKernelGGL(primal_generate_kernel, dim3((unsigned)((g.E + GEN_WAVES - 1) / GEN_WAVES)),
+                     dim3(64 * GEN_WAVES), 0, (hipStream_t)stream, g, a);
+  mapfx_note_kernel((const void*)primal_generate_kernel);
+  return check_hip(hipGetLastError(), "primal_generate_kernel launch");
 }
 
 }  // extern "C"

@@ -84,6 +84,12 @@ class QOut(ctypes.Structure):
                                     "err")]
 
 
+class QGen(ctypes.Structure):  # include/mapfx_primal.h mapfx_primal_gen
+    _fields_ = [("seed", c_u64), ("env_offset", c_i64), ("side_lut", c_vp), ("n_side", c_i32),
+                ("prob_lut", c_vp), ("n_prob", c_i32), ("episode", c_vp), ("mask", c_vp),
+                ("map_bits", c_vp), ("keep_map", c_i32), ("err", c_vp)]
+
+
 # every symbol include/mapfx.h, include/mapfx_partial.h and include/mapfx_primal.h declare
 # (checked by tests/test_abi_exports.py)
 EXPORTS = ("mapfx_abi_version", "mapfx_last_error", "mapfx_build_id", "mapfx_last_kernel",
@@ -98,7 +104,7 @@ EXPORTS = ("mapfx_abi_version", "mapfx_last_error", "mapfx_build_id", "mapfx_las
            "mapfx_partial_observe", "mapfx_primal_create", "mapfx_primal_destroy",
            "mapfx_primal_act", "mapfx_primal_act_timed", "mapfx_primal_observe",
            "mapfx_primal_blocking_count",
-           "mapfx_primal_blocking", "mapfx_runner_begin", "mapfx_runner_actions", "mapfx_runner_post",
+           "mapfx_primal_blocking", "mapfx_primal_generate", "mapfx_runner_begin", "mapfx_runner_actions", "mapfx_runner_post",
            "mapfx_runner_step", "mapfx_host_ring_alloc", "mapfx_host_ring_free")
 
 
@@ -164,6 +170,7 @@ def _load():
         "mapfx_primal_blocking_count": (c_i32, [c_vp, P(QState), c_vp, c_vp, c_vp]),
         "mapfx_primal_blocking": (c_i32, [c_vp, P(QState), c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp,
                                           c_vp, c_vp]),
+        "mapfx_primal_generate": (c_i32, [c_vp, P(QState), P(QGen), c_vp]),
         "mapfx_runner_begin": (c_i32, [P(RState), P(POut), P(ERows), c_vp]),
         "mapfx_runner_actions": (c_i32, [P(RState), c_vp, c_i32, c_i64, c_i32, P(ERows), c_vp]),
         "mapfx_runner_post": (c_i32, [P(RState), c_vp, P(POut), c_i32, c_vp, P(ERows), c_vp]),

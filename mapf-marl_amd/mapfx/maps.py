@@ -219,3 +219,32 @@ def primal_world(num_agents, SIZE=(10, 40), PROB=(0, .5), world0=None, blank_wor
     size = npr.choice([SIZE[0], SIZE[0] * .5 + SIZE[1] * .5, SIZE[1]], p=[.5, .25, .25])
     world = -(npr.rand(int(size), int(size)) < prob).astype(int)
     return world, _primal_place(world, num_agents, npr, pyr)
+
+
+def primal_gen_luts(SIZE=(10, 40), PROB=(0, .5), n_prob=256):
+    """(side_lut int32 [4], prob_lut uint32 [n_prob]): the tables with which the device
+    generator (mapfx_primal_generate, PrimalBatch.random / regenerate) draws the
+    reference's world distribution (:313-314) from two uniform indices.
+
+    * side_lut = [S0, S0, int(.5 S0 + .5 S1), S1]: p = (.5, .25, .25) exactly.
+    * prob_lut[i] = floor(2^32 * Finv((i + .5) / n_prob)), clipped to u32: the mid-point
+      quantiles of the triangular density with left P0, mode .33 P0 + .66 P1, right P1;
+      a cell is an obstacle when its 32-bit draw is below the entry.
+    Any other size / density curriculum is just another pair of tables (power-of-two
+    lengths)."""
+    s0, s1 = SIZE
+    side = np.array([s0, s0, int(s0 * .5 + s1 * .5), s1], dtype=np.int32)
+    n_prob = int(n_prob)
+    if n_prob < 1 or n_prob & (n_prob - 1):
+        raise ValueError("n_prob must be a power of two")
+    a, b = float(PROB[0]), float(PROB[1])
+    c = .33 * a + .66 * b
+    u = (np.arange(n_prob, dtype=np.float64) + .5) / n_prob
+    if b > a:
+        fc = (c - a) / (b - a)
+        q = np.where(u < fc, a + np.sqrt(u * (b - a) * (c - a)),
+                     b - np.sqrt((1. - u) * (b - a) * (b - c)))
+    else:
+        q = np.full(n_prob, a)
+    prob = np.clip(np.floor(q * 2.0 ** 32), 0, 2.0 ** 32 - 1).astype(np.uint32)
+    return side, prob

@@ -25,7 +25,7 @@ import torch
 
 from . import _abi
 from ._abi import check, lib, ptr
-from .maps import map_stride, pack_bits, primal_world
+from .maps import map_stride, pack_bits, primal_gen_luts, primal_world
 
 _OUT_KEYS = ("reward", "done", "next_mask", "on_goal", "valid", "obs", "vec")
 
@@ -92,6 +92,112 @@ class PrimalBatch:
         self.out = None
         self._Q = -1
         self.obs_out = None
+        # the device generator (regenerate): episode counters, and no tables until
+        # set_generator / PrimalBatch.random names the seed and the distribution
+        self.episode = torch.zeros((self.E,), dtype=torch.int32, device=dev)
+        self.gen_seed, self.env_offset = 0, 0
+        self.side_lut = self.prob_lut = None
+        self._generated = False
+
+    @classmethod
+    def random(cls, E, N, hw, seed, SIZE=(10, 40), PROB=(0, .5), observation_size=10,
+               diagonal=False, blocking=False, env_offset=0, device=None, luts=None):
+        """E random PRIMAL worlds of N agents drawn ON THE DEVICE (mapfx_primal_generate:
+        `_setWorld`, :248-341, by the rules of include/mapfx_primal.h) in an H x W handle,
+        hw = (H, W) <= (64, 64): sides and obstacle densities distributed as the
+        reference's SIZE / PROB (or by `luts` = (side_lut, prob_lut), power-of-two
+        lengths), agents on random free cells, every goal in its agent's connected
+        region.  World e is a function of (seed, env_offset + e, its episode counter)
+        alone.  Nothing of the generated state is read back or checked on the host."""
+        self = cls.__new__(cls)
+        self.blocking = bool(blocking)
+        self.device = torch.device(device if device is not None else "cuda")
+        if self.device.type != "cuda":
+            raise RuntimeError("PrimalBatch runs on a HIP device only (got %s)" % self.device)
+        self.E, self.N = int(E), int(N)
+        self.H, self.W = int(hw[0]), int(hw[1])
+        self.map_shared = False
+        self.s = int(observation_size)
+        self.diagonal = bool(diagonal)
+        self.n_actions = 9 if self.diagonal else 5
+        cfg = _abi.QCfg(H=self.H, W=self.W, n_agents=self.N, n_envs=self.E, obs_size=self.s,
+                        map_shared=0, diagonal=1 if self.diagonal else 0)
+        with torch.cuda.device(self.device):
+            h = ctypes.c_void_p()
+            check(lib.mapfx_primal_create(ctypes.byref(cfg), ctypes.byref(h)), "mapfx_primal_create")
+        self._h = h
+        dev = self.device
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+        self.bits = z((self.E, map_stride(self.H, self.W)), torch.uint8)
+        self.pos = z((self.E, self.N, 2), torch.int32)
+        self.goal = z((self.E, self.N, 2), torch.int32)
+        self.past = z((self.E, self.N, 2), torch.int32) if self.diagonal else None
+        self.err = z((1,), torch.int32)
+        self.episode = z((self.E,), torch.int32)
+        self._state = _abi.QState(pos=ptr(self.pos), goal=ptr(self.goal), map_bits=ptr(self.bits),
+                                  past=ptr(self.past))
+        self._K = -1
+        self.out = None
+        self._Q = -1
+        self.obs_out = None
+        self._generated = False
+        self.set_generator(seed, SIZE=SIZE, PROB=PROB, env_offset=env_offset, luts=luts)
+        self.regenerate()
+        return self
+
+    def set_generator(self, seed, SIZE=(10, 40), PROB=(0, .5), env_offset=0, luts=None):
+        """The seed, the global id of world 0 and the world distribution `regenerate`
+        draws from: the reference's SIZE / PROB (maps.primal_gen_luts), or `luts` =
+        (side_lut, prob_lut) of power-of-two lengths.  Tables given on the host are
+        checked here (every side in 1..min(H, W) with side^2 >= N: ValueError); device
+        tensors are taken as they are, and a bad side is reported per world by check_err()."""
+        self.gen_seed, self.env_offset = int(seed) & 0xFFFFFFFFFFFFFFFF, int(env_offset)
+        side, prob = primal_gen_luts(SIZE, PROB) if luts is None else luts
+        if not torch.is_tensor(side):
+            side = np.asarray(side, dtype=np.int32).reshape(-1)
+            lim = min(self.H, self.W)
+            if ((side < 1) | (side > lim)).any() or (side.astype(np.int64) ** 2 < self.N).any():
+                raise ValueError("world sides %s do not fit: need 1 <= side <= %d (the %dx%d handle) and "
+                                 "side^2 >= %d agents" % (side.tolist(), lim, self.H, self.W, self.N))
+            side = torch.as_tensor(side)
+        if not torch.is_tensor(prob):
+            prob = torch.as_tensor(np.asarray(prob, dtype=np.uint32).reshape(-1).view(np.int32))
+        # (torch has no uint32 arithmetic: the table travels as its int32 bit pattern)
+        self.side_lut = side.to(self.device).to(torch.int32).contiguous()
+        self.prob_lut = prob.to(self.device).contiguous()
+        if self.prob_lut.element_size() != 4 or self.prob_lut.ndim != 1 or self.side_lut.ndim != 1:
+            raise ValueError("side_lut / prob_lut must be 1-d tables of 32-bit entries")
+
+    def regenerate(self, mask=None, keep_map=False):
+        """A new episode, drawn on the device in one launch and in place (pos, goal, past,
+        the obstacle bitmaps, `episode`), for every world or for those with mask[e] != 0
+        (mask: [E], any integer / bool dtype, on the device -- e.g. out["done"][:, -1]);
+        a masked-out world is untouched.  keep_map=True is the reference's blank_world:
+        the obstacle maps stay (a shared map is allowed) and only agents and goals are
+        placed.  Asynchronous, no host synchronisation; a world that cannot be built (a
+        side that does not fit the handle or the agents, too few free cells under
+        keep_map) is left as it was and reported by check_err()."""
+        if not keep_map:
+            if self.map_shared:
+                raise ValueError("a shared-map batch regenerates with keep_map=True only")
+            if self.side_lut is None:
+                raise ValueError("no world distribution: call set_generator(seed, SIZE, PROB) first")
+        m = None
+        if mask is not None:
+            m = torch.as_tensor(mask, device=self.device)
+            if m.shape != (self.E,):
+                raise AssertionError("mask must be [%d]" % self.E)
+            m = (m if m.dtype == torch.uint8 else (m != 0).to(torch.uint8)).contiguous()
+        gen = _abi.QGen(seed=self.gen_seed, env_offset=self.env_offset,
+                        side_lut=ptr(self.side_lut), n_side=0 if self.side_lut is None else self.side_lut.numel(),
+                        prob_lut=ptr(self.prob_lut), n_prob=0 if self.prob_lut is None else self.prob_lut.numel(),
+                        episode=ptr(self.episode), mask=ptr(m), map_bits=ptr(self.bits),
+                        keep_map=1 if keep_map else 0, err=ptr(self.err))
+        with torch.cuda.device(self.device):
+            check(lib.mapfx_primal_generate(self._h, ctypes.byref(self._state), ctypes.byref(gen),
+                                            torch.cuda.current_stream().cuda_stream),
+                  "mapfx_primal_generate")
+        self._generated = True
 
     def _check_placement(self, starts, goals, bits):
         """Distinct in-bounds starts and goals on free cells: PRIMAL keeps agents,
@@ -220,6 +326,10 @@ class PrimalBatch:
         e = int(self.err.item())
         if e:
             self.err.zero_()
+            if self._generated:
+                raise AssertionError("invalid (agent_id, action), or a world the generator could not "
+                                     "build (a side that does not fit, too few free cells), for world %d"
+                                     % (e - 1))
             raise AssertionError("invalid (agent_id, action) for world %d" % (e - 1))
 
 

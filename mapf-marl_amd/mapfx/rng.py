@@ -17,6 +17,11 @@ K_AGENT = np.uint64(0x8CB92BA72F3D8DD7)
 K_CELL = np.uint64(0x9E6C63D0676A9A99)
 K_STREAM = np.uint64(0xF1357AEA2E62A9C5)
 
+# Streams of the device PRIMAL world generator (mapfx_primal_generate, csrc/primal.hip);
+# mapfx.maps uses 1..3.  The obstacle stream of redraw attempt t is STREAM_GEN_OBST + t,
+# t = 0..32.
+STREAM_GEN_WORLD, STREAM_GEN_OBST, STREAM_GEN_START, STREAM_GEN_GOAL = 0x100, 0x200, 0x300, 0x400
+
 
 def splitmix64(x):
     """Vectorised splitmix64 finaliser on uint64 arrays (wrapping arithmetic)."""
