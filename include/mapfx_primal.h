@@ -85,7 +85,20 @@ int mapfx_primal_create(const mapfx_primal_cfg* cfg, mapfx_primal_t** out_handle
 void mapfx_primal_destroy(mapfx_primal_t* h);
 
 /* K calls of MAPFEnv._step per world, in order: call k of world e is
- * (agent_ids[e][k] (1-based, as the reference), actions[e][k]). */
+ * (agent_ids[e][k] (1-based, as the reference), actions[e][k]).
+ * `out` and every member of it may be NULL (not produced); st->pos (and st->past) are
+ * updated all the same.  Only elements [e][0 .. K-1] of the outputs are written.
+ * A bad call -- an id outside 1..N, an action outside 0..4 (0..8 with cfg.diagonal); the
+ * reference asserts, :552-557 -- stops ITS world: *out->err is set to 1 + e (the first
+ * report wins), the calls of that world before it are complete, no output element of
+ * that world from the bad call on is written (the caller's bytes stay as they were), and
+ * st->pos / st->past of that world are the state after its last good call.  Every other
+ * world runs all its K calls.
+ * out->obs must be 4-byte aligned (MAPFX_EINVAL before any launch otherwise: the
+ * records leave as dwords).  The one-world-per-wave kernel (primal_seq_kernel: even
+ * obs_size 4..10, N <= 64, H and W + obs_size <= 64) writes 16-byte runs and is only
+ * taken when out->obs is 16-byte aligned or NULL; any other 4-byte aligned pointer gets
+ * the lane-group kernel (primal_act_kernel), with the same results. */
 int mapfx_primal_act(mapfx_primal_t* h, const mapfx_primal_state* st, const int32_t* agent_ids,
                      const int32_t* actions, int32_t K, const mapfx_primal_out* out, void* stream);
 

@@ -1837,6 +1837,8 @@ int mapfx_primal_act_timed(mapfx_primal_t* h, const mapfx_primal_state* st, cons
   if (!st || !st->pos || !st->goal || !st->map_bits) return perr(MAPFX_EINVAL, "bad state");
   if (h->geo.diag && !st->past) return perr(MAPFX_EINVAL, "diagonal movement needs state.past");
   if (K < 0) return perr(MAPFX_EINVAL, "K < 0");
+  // (both kernels write the observation records as dwords)
+  if (out && ((uintptr_t)out->obs & 3u)) return perr(MAPFX_EINVAL, "out->obs must be 4-byte aligned");
   if (K == 0 || h->geo.E == 0) return MAPFX_OK;
   if (!agent_ids || !actions) return perr(MAPFX_EINVAL, "NULL agent_ids / actions");
   QArgs a;
