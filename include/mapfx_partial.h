@@ -86,10 +86,12 @@ typedef struct mapfx_partial_state {
   int16_t* pnbr;            /* [E][N][4] goal_dist of the 4 neighbours (up, down,
                                left, right; an off-grid entry is unused) of each
                                agent's current cell, written with pdist by every
-                               launch: a step
+                               launch of the wave kernel: a step
                                takes a moving agent's npd from it instead of a
                                dependent table lookup.  Used only with pdist and
                                u8 / int16 tables (H*W <= 32767); NULL: looked up.
+                               The workgroup kernel (N > 64 or a side > 256)
+                               neither reads nor writes it.
                                Appended in ABI 4.                                  */
 } mapfx_partial_state;
 

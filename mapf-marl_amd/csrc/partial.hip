@@ -2075,31 +2075,43 @@ int mapfx_partial_goal_dist(mapfx_partial_t* h, const mapfx_partial_state* st,
   if ((long long)g.E * g.N == 0) return MAPFX_OK;
   const hipStream_t sm = (hipStream_t)stream;
   const dim3 grid((unsigned)(g.E * g.N));
+  const void* bfs = nullptr;  // the BFS instance launched (mapfx_last_kernel)
   if (g.huge_lds) {
-    if (g.gd32)
+    if (g.gd32) {
+      bfs = (const void*)partial_bfs_huge_kernel<int32_t>;
       hipLaunchKernelGGL(partial_bfs_huge_kernel<int32_t>, grid, dim3(HUGE_THREADS), g.huge_lds, sm, g,
                          st->map_bits, st->goal, env_mask, (int32_t*)st->goal_dist);
-    else
+    } else {
+      bfs = (const void*)partial_bfs_huge_kernel<int16_t>;
       hipLaunchKernelGGL(partial_bfs_huge_kernel<int16_t>, grid, dim3(HUGE_THREADS), g.huge_lds, sm, g,
                          st->map_bits, st->goal, env_mask, (int16_t*)st->goal_dist);
+    }
   } else if (g.H <= 64 && g.W <= 64) {
-    if (g.gd8)
+    if (g.gd8) {
+      bfs = (const void*)partial_bfs_kernel<uint8_t>;
       hipLaunchKernelGGL(partial_bfs_kernel<uint8_t>, grid, dim3(64), 0, sm, g, st->map_bits, st->goal,
                          env_mask, (uint8_t*)st->goal_dist);
-    else
+    } else {
+      bfs = (const void*)partial_bfs_kernel<int16_t>;
       hipLaunchKernelGGL(partial_bfs_kernel<int16_t>, grid, dim3(64), 0, sm, g, st->map_bits, st->goal,
                          env_mask, (int16_t*)st->goal_dist);
+    }
   } else {
-    if (g.gd32)
+    if (g.gd32) {
+      bfs = (const void*)partial_bfs_big_kernel<int32_t>;
       hipLaunchKernelGGL(partial_bfs_big_kernel<int32_t>, grid, dim3(256), 0, sm, g, st->map_bits,
                          st->goal, env_mask, (int32_t*)st->goal_dist);
-    else if (g.gd8)
+    } else if (g.gd8) {
+      bfs = (const void*)partial_bfs_big_kernel<uint8_t>;
       hipLaunchKernelGGL(partial_bfs_big_kernel<uint8_t>, grid, dim3(256), 0, sm, g, st->map_bits,
                          st->goal, env_mask, (uint8_t*)st->goal_dist);
-    else
+    } else {
+      bfs = (const void*)partial_bfs_big_kernel<int16_t>;
       hipLaunchKernelGGL(partial_bfs_big_kernel<int16_t>, grid, dim3(256), 0, sm, g, st->map_bits,
                          st->goal, env_mask, (int16_t*)st->goal_dist);
+    }
   }
+  mapfx_note_kernel(bfs);  // (not pdist_invalidate_kernel below)
   rc = check_hip(hipGetLastError(), "partial_bfs_kernel launch");
   if (rc || !st->pdist) return rc;
   const long long total = (long long)g.E * g.N;
