@@ -140,6 +140,11 @@ const char* mapfx_build_id(void);
  * packing, runner bookkeeping), exactly as rocprofv3 names it; "" before the first
  * launch.  Needs the HIP runtime (a visible device).  ABI 5. */
 const char* mapfx_last_kernel(void);
+/* How that launch got its actions (host-only bookkeeping, no device call): 2 = the split
+ * rollout staged the launch's int8 actions in LDS (a 16-byte aligned buffer, T <= 64, LDS
+ * to spare), 1 = the split rollout read them in register blocks, 0 = the device generator
+ * or any other kernel. */
+int mapfx_last_action_path(void);
 
 /* Bytes of one env's obstacle bitmap: ceil(H*W/8) rounded up to 16. */
 int64_t mapfx_map_stride(int32_t H, int32_t W);

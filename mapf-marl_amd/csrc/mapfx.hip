@@ -49,6 +49,9 @@ thread_local std::string g_last_error;
 
 // the host stub of the calling thread's most recent launch (mapfx_last_kernel)
 thread_local const void* g_last_kernel = nullptr;
+// ... and how that launch got its actions (mapfx_last_action_path): 0 = the device generator
+// or a kernel other than the split rollout, 1 = register blocks, 2 = staged in LDS
+thread_local int g_last_action_path = 0;
 
 int set_error(int code, const char* fmt, ...) {
   char buf[512];
@@ -151,6 +154,7 @@ struct Args {
   int32_t* traj_t;
   int32_t* err;
   const double* pow_lut;
+  int act_stage;  // split rollout: the launch's int8 actions are staged in LDS (launch())
 };
 
 // The pointers a launch reads first also travel as leading scalar kernel parameters:
@@ -163,7 +167,8 @@ struct Args {
 // ... and what the first loads' addresses need: hp_geo = H | W << 13 | P << 26 |
 // wv_fast << 31 (the bitmap stride follows from H, W: mapfx_map_stride) and hp_nm =
 // grid size | (T >= 16) << 26 | act_dtype << 27 | do_step << 29 | use_rng << 30 |
-// map_shared << 31 (the XCD-aware block order needs the grid size, gridDim comes from
+// map_shared << 31 (the free dtype code 3 stands for int8 actions staged in LDS, act_stage;
+// the XCD-aware block order needs the grid size, gridDim comes from
 // the implicit kernargs; a rollout of at least 16 steps fetches its first action block
 // without a clamp to T, and with every env full E = grid size x envs per block, so the
 // first action loads need no kernarg from memory either).  14 dwords: all that
@@ -175,13 +180,15 @@ struct Args {
   (g).P = (int)((hp_geo >> 26) & 0x1Fu), (g).wv_fast = (int)(hp_geo >> 31),                \
   (g).bits_words = ((g).H * (g).W + 31) >> 5, (g).map_shared = 0,                           \
   (g).map_stride = (hp_nm >> 31) ? 0 : ((((g).H * (g).W + 7) >> 3) + 15) & ~15,            \
-  (g).nblk = (int)(hp_nm & 0x3FFFFFFu), (a).act_dtype = (int)((hp_nm >> 27) & 3u),         \
+  (g).nblk = (int)(hp_nm & 0x3FFFFFFu), (a).act_stage = ((hp_nm >> 27) & 3u) == 3u,         \
+  (a).act_dtype = (a).act_stage ? MAPFX_I8 : (int)((hp_nm >> 27) & 3u),                     \
   (a).do_step = (int)((hp_nm >> 29) & 1u), (a).use_rng = (int)((hp_nm >> 30) & 1u)
 #define MAPFX_HOT_ARGS(a, g, nb)                                                             \
   (a).pos, (a).goal, (a).done, (a).bits, (a).actions, (a).t,                                \
       (uint32_t)(g).H | ((uint32_t)(g).W << 13) | ((uint32_t)(g).P << 26) |                 \
           ((uint32_t)(g).wv_fast << 31),                                                    \
-      (uint32_t)(nb) | ((a).T >= 16 ? 1u << 26 : 0u) | ((uint32_t)((a).act_dtype & 3) << 27) |   \
+      (uint32_t)(nb) | ((a).T >= 16 ? 1u << 26 : 0u) |                                      \
+          ((uint32_t)((a).act_stage ? 3 : (a).act_dtype & 3) << 27) |                      \
           ((a).do_step ? 1u << 29 : 0u) | ((a).use_rng ? 1u << 30 : 0u) | ((g).map_shared ? 1u << 31 : 0u)
 
 template <typename CellT>
@@ -1465,6 +1472,8 @@ __device__ __forceinline__ void stage_occ_record(const uint32_t (&R)[(WIN * WIN 
 // published a barrier late, a MOVE / MAP step side, nontemporal stores) were slower and
 // are gone from the source; their numbers are in DESIGN.md §4.1b.
 constexpr int SPLIT_WAVES = 3;               // step wave + two store waves
+constexpr int SPLIT_WG_PER_CU = 4;           // resident workgroups per CU the split is built for
+                                             // (__launch_bounds__: SPLIT_WAVES waves per SIMD)
 constexpr int SPLIT_DBM_INFO = 2 * 64 * 16;  // info words of two steps
 constexpr int SPLIT_DBM_EDGE = 3 * 64;       // edge counts of two steps + the launch's last step
 // reward-code table + 32-step code ring: u8 codes (edge <= 15: 16 agents per env) and a
@@ -1477,6 +1486,60 @@ constexpr uint32_t SF_DONE = 1, SF_LIVE = 2, SF_DNOLD = 4, SF_ENVC = 8, SF_SKIP 
 // Workgroup barrier that waits for this wave's LDS traffic only: outstanding
 // global stores stay in flight (a __syncthreads() would drain them every step).
 __device__ __forceinline__ void split_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// ---- action staging: a launch's int8 actions in LDS, fetched once in the prologue ----
+// With every lane group full the workgroup's envs (64 / LL envs of LL agents) own 64
+// contiguous bytes of each [E][N] action row.  The three waves fetch rows 0 .. T - 1 with
+// 16-byte loads -- lane t of 192 takes quarter t & 3 of row t >> 2, SPLIT_STAGE_ROWS rows
+// per pass -- and write them behind the fold region before the prologue barrier:
+//   [SPLIT_STAGE_FLAGS bytes: one "holds an action > 4" flag per wave][T rows of 64 bytes]
+// The step wave then reads step s's action as the byte rows[s * 64 + lane]: its loop holds
+// no global load and no vmcnt wait.  A row >= T is never read from memory.
+constexpr int SPLIT_STAGE_ROWS = 64 * SPLIT_WAVES / 4;
+// Launches past 64 steps keep the register blocks: there the store stream slows down for
+// both paths (C2's outputs outgrow the 256 MB last-level cache) and the staged launch
+// measured slower, 86.6 vs 80.7 us at T = 96 and 121.4 vs 108.7 us at T = 128
+// (profiles/action_staging_tsweep_c2.txt, taken with a cap of 128).
+constexpr int SPLIT_STAGE_MAX_T = 64;
+constexpr int SPLIT_STAGE_PASSES = (SPLIT_STAGE_MAX_T + SPLIT_STAGE_ROWS - 1) / SPLIT_STAGE_ROWS;
+constexpr int SPLIT_STAGE_FLAGS = 16;
+__host__ __device__ constexpr int split_stage_lds(int T) { return SPLIT_STAGE_FLAGS + 64 * T; }
+// the split's LDS between its second maps and the staged actions
+__host__ __device__ constexpr int split_tail_lds(int recb, int L) {
+  return SPLIT_DBM_INFO + SPLIT_DBM_EDGE + 2 * 64 * recb + split_fold_lds(L);
+}
+typedef unsigned int stage_v4 __attribute__((ext_vector_type(4)));
+constexpr uint32_t SPLIT_STAGE_STAY = 0x04040404u;  // four "stay" actions: a pass not loaded
+
+// passes `first` .. of this lane: src = the workgroup's bytes of row 0 + the lane's quarter,
+// row0 = t >> 2, wrow (wave-uniform) = the wave's first row of a pass.  Row indices are
+// clamped below T, so a partial last pass re-reads row T - 1 instead of the row behind it.
+__device__ __forceinline__ void stage_issue(stage_v4 (&v)[SPLIT_STAGE_PASSES], const unsigned char* src,
+                                            uint32_t EN, int T, int row0, int wrow, int first) {
+#pragma unroll
+  for (int p = 0; p < SPLIT_STAGE_PASSES; ++p)
+    if (p >= first && p * SPLIT_STAGE_ROWS + wrow < T)
+      v[p] = *(const stage_v4*)__builtin_assume_aligned(
+          src + (uint32_t)min(p * SPLIT_STAGE_ROWS + row0, T - 1) * EN, 16);
+}
+
+// the fetched rows to LDS, and this wave's flag: any byte > 4 (unsigned) in what it fetched
+__device__ __forceinline__ void stage_commit(const stage_v4 (&v)[SPLIT_STAGE_PASSES], unsigned char* stage,
+                                             int T, int row0, int wave, int lane) {
+  uint32_t bad = 0;
+#pragma unroll
+  for (int p = 0; p < SPLIT_STAGE_PASSES; ++p) {
+    const uint32_t w[4] = {v[p].x, v[p].y, v[p].z, v[p].w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i)  // bits 3-7 set, or the low three bits >= 5
+      bad |= (w[i] & 0xF8F8F8F8u) | (((w[i] & 0x07070707u) + 0x03030303u) & 0x08080808u);
+    const int r = p * SPLIT_STAGE_ROWS + row0;
+    if (r < T)
+      *(stage_v4*)__builtin_assume_aligned(stage + SPLIT_STAGE_FLAGS + r * 64 + 16 * (lane & 3), 16) = v[p];
+  }
+  const bool any = __ballot(bad != 0) != 0;
+  if (lane == 0) stage[wave] = any ? 1 : 0;
+}
 
 template <typename P, typename V>
 __device__ __forceinline__ void split_store(P p, V v) {
@@ -1707,6 +1770,18 @@ __global__ void __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : 64, SPLIT ? SPLIT_W
   if constexpr (SPLIT) {
     if (threadIdx.x >= 64) {  // the output side of the split
       const int e0 = xcd_block(blockIdx.x, g.nblk) * (64 / LL);
+      constexpr int RECB = OCC ? WIN * WIN : 2 * WIN * WIN;  // one wave's staged image: 64 * RECB
+      // this wave's share of the launch's action rows (after the map words, whose loads
+      // wait for no kernarg from memory: T does)
+      stage_v4 sv[SPLIT_STAGE_PASSES];
+#pragma unroll
+      for (int p = 0; p < SPLIT_STAGE_PASSES; ++p) sv[p] = stage_v4{SPLIT_STAGE_STAY, SPLIT_STAGE_STAY, SPLIT_STAGE_STAY, SPLIT_STAGE_STAY};
+      const int swave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+      const auto stage_fetch = [&]() __attribute__((always_inline)) {
+        if (a.act_stage)
+          stage_issue(sv, (const unsigned char*)a.actions + (uint32_t)e0 * LL + 16u * (threadIdx.x & 3),
+                      (uint32_t)g.nblk * 64u, a.T, (int)(threadIdx.x >> 2), 16 * swave, 0);
+      };
       if (g.wv_fast) {  // the store waves build their share of the padded maps (rows
         // ag + 16 w of each env, w = this wave's index: the step wave takes w = 0), then
         // the barrier the step wave meets after its own rows
@@ -1719,12 +1794,17 @@ __global__ void __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : 64, SPLIT ? SPLIT_W
         // (as in the step wave, below; + the step wave's LDS offsets, dead here)
         asm volatile("" ::"s"(g0.map_words), "s"(a0.do_step), "s"(g0.wv_off_dep), "s"(g0.wv_off_bits),
                      "s"(g0.wv_off_rew));
+        stage_fetch();
         build_map_rows_fast<MAPFX_FAST_WPR, 1>(g, (uint32_t*)(lds + g.wv_off_map + sl * g.map_env_bytes), src,
                                                bl, LL * SPLIT_WAVES, pf,
                                                (uint32_t*)(lds + g.wv_off_split + sl * g.map_env_bytes));
+      } else {
+        stage_fetch();
       }
-      split_barrier();
-      constexpr int RECB = OCC ? WIN * WIN : 2 * WIN * WIN;  // one wave's staged image: 64 * RECB
+      if (a.act_stage)
+        stage_commit(sv, lds + g.wv_off_split + (64 / LL) * g.map_env_bytes + split_tail_lds(RECB, LL), a.T,
+                     (int)(threadIdx.x >> 2), swave, (int)(threadIdx.x & 63));
+      split_barrier();  // + the staged actions and the waves' flags
       const int par = (int)(threadIdx.x >> 6) - 1;            // this wave's step parity
       // [M1: 64 / LL maps][info: 2 steps][edge: 2 steps][staged records: 2 waves][fold]
       unsigned char* m1 = lds + g.wv_off_split;
@@ -1765,18 +1845,36 @@ __global__ void __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : 64, SPLIT ? SPLIT_W
   // loads wait for no kernarg fetch)
   const uint32_t EN = FULLW ? (uint32_t)g.nblk * (uint32_t)(EPW * N) : (uint32_t)(g.E * N);
   const bool t_long = ROLL && ((hp_nm >> 26) & 1u);  // T >= 16 >= AB
-  // Actions are fetched for AB steps at a time: one VMEM wait per block instead of
-  // one per step (a wait on a per-step load would also drain the step's stores).
+  // The split kernel stages a launch's int8 actions in LDS once (stage_issue / stage_commit
+  // above; launch() decides): this wave's rows 0 .. 15 are issued first of all when
+  // T >= 16 (no clamp to T, a kernarg from memory), the rest after the state loads.
+  bool stage = false;
+  stage_v4 sv[SPLIT_STAGE_PASSES], sv0e;
+  const unsigned char* ssrc = nullptr;
+  if constexpr (SPLIT) {
+    stage = a.act_stage != 0;
+    sv0e = stage_v4{SPLIT_STAGE_STAY, SPLIT_STAGE_STAY, SPLIT_STAGE_STAY, SPLIT_STAGE_STAY};
+#pragma unroll
+    for (int p = 0; p < SPLIT_STAGE_PASSES; ++p) sv[p] = sv0e;
+    ssrc = (const unsigned char*)a.actions + (uint32_t)env0 * LL + 16u * (lane64 & 3);
+    if (stage && t_long) sv0e = *(const stage_v4*)__builtin_assume_aligned(ssrc + (uint32_t)(lane64 >> 2) * EN, 16);
+  }
+  // Otherwise actions are fetched for AB steps at a time: one VMEM wait per block instead
+  // of one per step (a wait on a per-step load would also drain the step's stores).
   constexpr int MAPFX_AB = 16;
   constexpr int AB = ROLL ? (ABT > 0 ? ABT : MAPFX_AB) : 1;
   static_assert(AB <= 16, "t_long: the first action block lies within T >= 16 steps");
   uint32_t actpk[(AB + 3) / 4];
-  // Action blocks from memory are prefetched one block ahead: block 0 is issued
-  // first of all (its HBM latency overlaps the state loads and the map build; issued
-  // after them, step 0 still waited ~900 cycles for it at C2 T = 20), block b + 1 as
-  // soon as block b is unpacked, so the wait at a block boundary finds it arrived.
+  // Action blocks from memory are fetched a block ahead: block 0 is issued first of all
+  // (its HBM latency overlaps the state loads and the map build; issued after them, step 0
+  // still waited ~900 cycles for it at C2 T = 20), block b + 1 when block b is unpacked.
+  // That second fetch is NOT asynchronous in the compiled code: the conditional fetch makes
+  // nxt a phi of "just loaded" and "unchanged", the copy that resolves it lands in the
+  // boundary code behind an s_waitcnt vmcnt(0), and the step wave sits out one global-load
+  // round trip per block boundary (about 1.1 us under the store stream; the first, before
+  // step 0, about 0.7 us).  The staged path above has no such wait.
   int nxt[AB];
-  const bool act_mem = do_step && !a.use_rng;
+  const bool act_mem = do_step && !a.use_rng && !stage;
   // block 0 of an int8 launch of >= 16 steps: no clamp to T (a kernarg from memory)
   const bool first_early = act_mem && ROLL && t_long && a.act_dtype == MAPFX_I8;
   if (first_early) {
@@ -1843,6 +1941,9 @@ __global__ void __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : 64, SPLIT ? SPLIT_W
   if (act_mem && ROLL && !first_early) fetch(0);  // (one step: after the state loads -- a
                                                   // non-int8 action is range-checked at its
                                                   // load, which would wait for it here)
+  if constexpr (SPLIT) {  // the staged rows that need T
+    if (stage) stage_issue(sv, ssrc, EN, T, lane64 >> 2, 0, t_long ? 1 : 0);
+  }
   int cur = 0, gcell = -1, st = 0;  // padded cell of the agent / of its goal
   if (has) {
     cur = cell0 + p0.x * pitch + p0.y;
@@ -1870,8 +1971,18 @@ __global__ void __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : 64, SPLIT ? SPLIT_W
     wave_fence();
     for (int w = ag; w < (g.map_env_bytes >> 2); w += L) m1_32[w] = map32[w];
   }
-  if constexpr (SPLIT) split_barrier();  // + the store waves' rows
-  else wave_fence();
+  // the staged actions behind the fold region (the store waves write their rows likewise)
+  unsigned char* const stg =
+      SPLIT ? lds + g.wv_off_split + EPW * g.map_env_bytes + split_tail_lds(SPLIT && OCC ? WW : REC, LL) : nullptr;
+  if constexpr (SPLIT) {
+    if (stage) {
+      if (t_long) sv[0] = sv0e;
+      stage_commit(sv, stg, T, lane64 >> 2, 0, lane64);
+    }
+    split_barrier();  // + the store waves' map rows, action rows and flags
+  } else {
+    wave_fence();
+  }
   PSTAMP(2);
   if (has) atomicAdd(&map32[cur >> 2], 1u << ((cur & 3) * 8));
   if (DBM && has) atomicAdd(&m1_32[cur >> 2], 1u << ((cur & 3) * 8));
@@ -2042,7 +2153,8 @@ __global__ void __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : 64, SPLIT ? SPLIT_W
       } else if (a.use_rng) {
 #pragma unroll
         for (int k = 0; k < AB; ++k) v[k] = gen_action(a.seed, g.env_offset + env, a.t0 + s + k, ag);
-      } else {  // the prefetched block; the next one is issued right away
+      } else {  // the fetched block; the next one is issued here -- and, as compiled, waited
+                // for before this block's first step (see nxt above)
 #pragma unroll
         for (int k = 0; k < AB; ++k) v[k] = nxt[k];
         if (ROLL && s + AB < T) fetch(s + AB);
@@ -2079,14 +2191,19 @@ __global__ void __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : 64, SPLIT ? SPLIT_W
     // branch outside the loop, and the per-step ballot for an invalid action (the env
     // skips the step, :91-92) runs only in an action block that holds one (blk_bad, from
     // the block's unpack) -- the step wave's chain paces the launch.
+    // With staged actions (STG) the check is decided once per launch from the three
+    // waves' staging flags, and step s's action is the LDS byte read during step s - 1.
     bool blk_bad = false;
+    int act_nx = 4;
+    const unsigned char* const srows = stg + SPLIT_STAGE_FLAGS + lane64;
     const auto unpack_block = [&](int s_) __attribute__((always_inline)) {  // steps s .. s+AB-1, 4 per u32
       const int s = __builtin_amdgcn_readfirstlane(s_);  // (wave-uniform)
       int v[AB];
       if (a.use_rng) {
 #pragma unroll
         for (int k = 0; k < AB; ++k) v[k] = gen_action(a.seed, g.env_offset + env, a.t0 + s + k, ag);
-      } else {  // the prefetched block; the next one is issued right away
+      } else {  // the fetched block; the next one is issued here -- and, as compiled, waited
+                // for before this block's first step (see nxt above)
 #pragma unroll
         for (int k = 0; k < AB; ++k) v[k] = nxt[k];
         if (s + AB < T) fetch(s + AB);
@@ -2104,10 +2221,11 @@ __global__ void __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : 64, SPLIT ? SPLIT_W
       }
       blk_bad = __builtin_amdgcn_readfirstlane(__ballot((bad & 0x80u) != 0) != 0 ? 1 : 0) != 0;
     };
-    const auto step = [&](auto odd_c, auto ar_c, auto chk_c, int s) __attribute__((always_inline)) {
+    const auto step = [&](auto odd_c, auto ar_c, auto chk_c, auto stg_c, int s) __attribute__((always_inline)) {
       constexpr bool ODD = decltype(odd_c)::value;  // map s & 1
       constexpr bool AR = decltype(ar_c)::value;    // autoreset
-      constexpr bool CHK = decltype(chk_c)::value;  // the block holds an invalid action
+      constexpr bool CHK = decltype(chk_c)::value;  // the block / the launch holds an invalid action
+      constexpr bool STG = decltype(stg_c)::value;  // actions staged in LDS
       unsigned char* mp = ODD ? m1 : map;
       uint32_t* mp32 = (uint32_t*)mp;
       int& cpr = ODD ? cp1 : cp0;
@@ -2129,11 +2247,17 @@ __global__ void __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : 64, SPLIT ? SPLIT_W
           reset_pending = false;
         }
       }
-      const int act = (int)(actpk[0] & 0xFFu);
+      int act;
+      if constexpr (STG) {
+        act = act_nx;
+        if constexpr (CHK) act = (uint32_t)act > 4u ? 0xFF : act;  // (the reference asserts, :92)
+      } else {
+        act = (int)(actpk[0] & 0xFFu);
 #pragma unroll
-      for (int k = 0; k < (AB + 3) / 4; ++k)  // shift the packed actions down one byte
-        actpk[k] = (k + 1 < (AB + 3) / 4) ? __builtin_amdgcn_alignbit(actpk[k + 1], actpk[k], 8)
-                                          : (actpk[k] >> 8);
+        for (int k = 0; k < (AB + 3) / 4; ++k)  // shift the packed actions down one byte
+          actpk[k] = (k + 1 < (AB + 3) / 4) ? __builtin_amdgcn_alignbit(actpk[k + 1], actpk[k], 8)
+                                            : (actpk[k] >> 8);
+      }
       STAMP(0);
       // A: move decision on the pre-step neighbours (:319-342), this map's count moves
       const int oc = cur;
@@ -2156,6 +2280,7 @@ __global__ void __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : 64, SPLIT ? SPLIT_W
       // occupant's move (the edge test)
       const uint32_t n_up = mp[nc - pitch], n_dw = mp[nc + pitch], n_lf = mp[nc - 1], n_rt = mp[nc + 1];
       const uint32_t dj = dep[nc];
+      if constexpr (STG) act_nx = srows[min(s + 1, T - 1) * 64];  // the next step's action
       STAMP(1);
       // C: step s - 1's edge count (:364-383), for the store wave's b part (counting it in
       // the store waves' a part instead, from old / new cell, action and the occupant's move
@@ -2209,16 +2334,36 @@ __global__ void __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : 64, SPLIT ? SPLIT_W
     const auto run = [&](auto ar_c) __attribute__((always_inline)) {
       for (int s = 0; s < T; s += 2) {
         if ((s & (AB - 1)) == 0) unpack_block(s);
-        if (blk_bad) step(F_{}, ar_c, T_{}, s);
-        else step(F_{}, ar_c, F_{}, s);
+        if (blk_bad) step(F_{}, ar_c, T_{}, F_{}, s);
+        else step(F_{}, ar_c, F_{}, F_{}, s);
         if (s + 1 < T) {
-          if (blk_bad) step(T_{}, ar_c, T_{}, s + 1);
-          else step(T_{}, ar_c, F_{}, s + 1);
+          if (blk_bad) step(T_{}, ar_c, T_{}, F_{}, s + 1);
+          else step(T_{}, ar_c, F_{}, F_{}, s + 1);
         }
       }
     };
-    if (a.autoreset) run(T_{});
-    else run(F_{});
+    const auto run_staged = [&](auto ar_c, auto chk_c) __attribute__((always_inline)) {
+      for (int s = 0; s < T; s += 2) {
+        step(F_{}, ar_c, chk_c, T_{}, s);
+        if (s + 1 < T) step(T_{}, ar_c, chk_c, T_{}, s + 1);
+      }
+    };
+    if (stage) {
+      // (byte 3 of the flag word is no wave's)
+      const bool bad = __builtin_amdgcn_readfirstlane(*(const uint32_t*)stg & 0xFFFFFFu) != 0;
+      act_nx = srows[0];
+      if (a.autoreset) {
+        if (bad) run_staged(T_{}, T_{});
+        else run_staged(T_{}, F_{});
+      } else {
+        if (bad) run_staged(F_{}, T_{});
+        else run_staged(F_{}, F_{});
+      }
+    } else if (a.autoreset) {
+      run(T_{});
+    } else {
+      run(F_{});
+    }
     ((int2*)a.pos)[oa] = cell_rc(cur);
     a.done[oa] = dn ? 1 : 0;
     if (a.steps) a.steps[oa] = st;
@@ -2581,14 +2726,25 @@ int launch(mapfx_t* h, Args& a, bool roll, hipStream_t stream, hipEvent_t ev0 = 
     KernelFn fn = pick_wave_kernel((a.obs_window || occ) ? g.window : 0, roll, fullw, runner, g.L, split, occ,
                                    roll && a.T <= MAPFX_AB_SHORT_T);
     if (fn) {
+      // Staged actions (split rollout, int8 buffer, 16-byte aligned, T <= 64): 16 + 64 T
+      // more LDS bytes, taken only while they leave the resident workgroups per CU (160 KB
+      // of LDS) as they are, counted up to the SPLIT_WG_PER_CU the kernel is built for --
+      // C2: 31,168 B, 35,280 B staged at T = 64, four per CU either way
+      const int stage_lds = split ? split_lds + split_stage_lds(a.T) : 0;
+      const auto resident = [](int lds) { return std::min(SPLIT_WG_PER_CU, 160 * 1024 / lds); };
+      a.act_stage = split && a.do_step && !a.use_rng && a.act_dtype == MAPFX_I8 &&
+                            ((uintptr_t)a.actions & 15) == 0 && a.T >= 1 && a.T <= SPLIT_STAGE_MAX_T &&
+                            stage_lds <= 64 * 1024 && resident(stage_lds) == resident(split_lds)
+                        ? 1 : 0;
       const int blocks = (g.E + g.EPW - 1) / g.EPW;
       const dim3 bt(split ? 64 * SPLIT_WAVES : 64);
-      const unsigned ldsb = split ? split_lds : g.wv_lds;
+      const unsigned ldsb = a.act_stage ? stage_lds : split ? split_lds : g.wv_lds;
       if (ev0 || ev1)
         hipExtLaunchKernelGGL(fn, dim3(blocks), bt, ldsb, stream, ev0, ev1, 0, MAPFX_HOT_ARGS(a, g, blocks), a, g);
       else
         hipLaunchKernelGGL(fn, dim3(blocks), bt, ldsb, stream, MAPFX_HOT_ARGS(a, g, blocks), a, g);
       g_last_kernel = (const void*)fn;
+      g_last_action_path = a.act_stage ? 2 : (split && !a.use_rng) ? 1 : 0;
       return check_hip(hipGetLastError(), "mapf_wave_kernel launch");
     }
   }
@@ -2604,6 +2760,7 @@ int launch(mapfx_t* h, Args& a, bool roll, hipStream_t stream, hipEvent_t ev0 = 
   else
     hipLaunchKernelGGL(fn, dim3(blocks), dim3(g.BT), lds, stream, MAPFX_HOT_ARGS(a, g, blocks), a, g);
   g_last_kernel = (const void*)fn;
+  g_last_action_path = 0;
   return check_hip(hipGetLastError(), roll ? "mapf_rollout_kernel launch" : "mapf_step_kernel launch");
 }
 
@@ -2668,7 +2825,12 @@ int mapfx_abi_version(void) { return MAPFX_ABI_VERSION; }
 #endif
 const char* mapfx_build_id(void) { return MAPFX_BUILD_ID; }
 
-void mapfx_note_kernel(const void* fn) { g_last_kernel = fn; }
+void mapfx_note_kernel(const void* fn) {
+  g_last_kernel = fn;
+  g_last_action_path = 0;
+}
+
+int mapfx_last_action_path(void) { return g_last_action_path; }
 
 const char* mapfx_last_kernel(void) {
   thread_local std::string name;

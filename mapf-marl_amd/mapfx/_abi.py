@@ -93,6 +93,7 @@ class QGen(ctypes.Structure):  # include/mapfx_primal.h mapfx_primal_gen
 # every symbol include/mapfx.h, include/mapfx_partial.h and include/mapfx_primal.h declare
 # (checked by tests/test_abi_exports.py)
 EXPORTS = ("mapfx_abi_version", "mapfx_last_error", "mapfx_build_id", "mapfx_last_kernel",
+           "mapfx_last_action_path",
            "mapfx_map_stride", "mapfx_obs_elem_size",
            "mapfx_edge_elem_size",
            "mapfx_create", "mapfx_destroy", "mapfx_query", "mapfx_reset", "mapfx_step",
@@ -138,6 +139,7 @@ def _load():
         "mapfx_last_error": (ctypes.c_char_p, []),
         "mapfx_build_id": (ctypes.c_char_p, []),
         "mapfx_last_kernel": (ctypes.c_char_p, []),
+        "mapfx_last_action_path": (c_i32, []),
         "mapfx_map_stride": (c_i64, [c_i32, c_i32]),
         "mapfx_obs_elem_size": (c_i32, [c_i32]),
         "mapfx_edge_elem_size": (c_i32, [c_i32]),
@@ -206,6 +208,12 @@ def build_id() -> str:
 def last_kernel() -> str:
     """mapfx_last_kernel(): the rocprofv3 name of this thread's last env-kernel launch."""
     return lib.mapfx_last_kernel().decode()
+
+
+def last_action_path() -> int:
+    """mapfx_last_action_path(): how this thread's last env launch got its actions -- 2 staged
+    in LDS, 1 register blocks (split rollout), 0 the device generator or another kernel."""
+    return int(lib.mapfx_last_action_path())
 
 
 def ptr(t) -> int | None:
