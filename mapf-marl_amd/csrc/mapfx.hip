@@ -1469,8 +1469,9 @@ __device__ __forceinline__ void stage_occ_record(const uint32_t (&R)[(WIN * WIN 
 // per-agent reward codes.  One barrier per step (LDS traffic only), so the step wave
 // issues no global store inside its loop and the stores stay in flight across barriers.
 // Measured alternatives (a 2-wave form, a single image of raw window rows, a 3-slot ring
-// published a barrier late, a MOVE / MAP step side, nontemporal stores) were slower and
-// are gone from the source; their numbers are in DESIGN.md §4.1b.
+// published a barrier late, a MOVE / MAP step side, nontemporal stores, the per-agent
+// outputs gathered through LDS into 16-byte write-through stores) were slower and are gone
+// from the source; their numbers are in DESIGN.md §4.1b.
 constexpr int SPLIT_WAVES = 3;               // step wave + two store waves
 constexpr int SPLIT_WG_PER_CU = 4;           // resident workgroups per CU the split is built for
                                              // (__launch_bounds__: SPLIT_WAVES waves per SIMD)
@@ -1541,9 +1542,29 @@ __device__ __forceinline__ void stage_commit(const stage_v4 (&v)[SPLIT_STAGE_PAS
   if (lane == 0) stage[wave] = any ? 1 : 0;
 }
 
-template <typename P, typename V>
+// Store policy of the store waves ("Store policy").  PLAIN leaves the line
+// dirty in the XCD's L2: right for the tiny per-env outputs, whose partial lines merge there.
+// WT writes through and drops the line -- the window records (16 bytes per lane, sc0 sc1)
+// and the per-agent outputs (1 or 8 bytes per lane, each instruction a contiguous 64 or
+// 512 bytes of the wave; a relaxed agent-scope atomic store is the compiler's sc1 store).
+enum class SplitSt { PLAIN, WT };
+template <SplitSt POL = SplitSt::PLAIN, typename P, typename V>
 __device__ __forceinline__ void split_store(P p, V v) {
-  *p = v;
+  if constexpr (POL == SplitSt::WT) {
+    static_assert(sizeof(V) <= 8, "wider values: split_store_wt16");
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  } else {
+    *p = v;
+  }
+}
+// WT, 16 bytes at byte `off` (< 2^32: launch()'s fits32) of one output array, through a
+// buffer resource (no builtin stores 16 bytes write-through to a plain global address)
+typedef unsigned int split_u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t split_rsrc(void* base) {
+  return __builtin_amdgcn_make_buffer_rsrc(base, 0, -1, 0x00027000);  // raw, no range limit, 32-bit format
+}
+__device__ __forceinline__ void split_store_wt16(__amdgpu_buffer_rsrc_t r, uint32_t off, split_u32x4 v) {
+  __builtin_amdgcn_raw_buffer_store_b128(v, r, (int)off, 0, 17);  // aux 17 = sc0 | sc1
 }
 
 // padded LDS cell index -> (row, col); cell < 2^16, pitch < 256
@@ -1562,6 +1583,8 @@ __device__ __forceinline__ int2 padded_cell_rc(const Geo& g, int cell) {
 //   b(q), the interval after barrier q + 2: the edge count (the step wave computes it in
 //     iteration q + 1), the reward code, the staged record out with lane-contiguous
 //     16-byte stores, every per-agent and per-env output, and every 16th step the fold.
+// Records and per-agent outputs are written through, the per-env outputs are plain stores
+// (split_store, above).
 template <int WIN, int LL, bool OCC>
 __device__ __forceinline__ void split_store_wave_dbm(const Geo& g, const Args& a, const unsigned char* m0,
                                                      const unsigned char* m1, const unsigned char* info,
@@ -1570,7 +1593,6 @@ __device__ __forceinline__ void split_store_wave_dbm(const Geo& g, const Args& a
                                                      int lane, int par) {
   typedef __attribute__((address_space(1))) unsigned char gbyte;
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-  typedef int i32x2 __attribute__((ext_vector_type(2)));
   constexpr int H2 = WIN / 2, REC = OCC ? WIN * WIN : 2 * WIN * WIN;
   constexpr int RCH = 4 * REC;  // 16-byte chunks of the wave's 64 records
   constexpr int NRC = (RCH + 63) / 64;
@@ -1588,6 +1610,7 @@ __device__ __forceinline__ void split_store_wave_dbm(const Geo& g, const Args& a
   const u32x4* inf = (const u32x4*)__builtin_assume_aligned(info, 16);
   const int pitch = g.pitch, wpr = g.pitch >> 2;
   uint32_t k_nc = 0, k_nb = 0, k_fl = 0, k_t = 0, k_node = 0;  // step q's, kept from a to b
+  const __amdgpu_buffer_rsrc_t rrec = split_rsrc(OCC ? a.obs_window_occ : a.obs_window);
 
   for (int c = lane + 64 * par; c < NCODE; c += 128) {  // the code reward table (as the ALT waves)
     double rr = 0.0;  // exact fp64 op order of the reference
@@ -1668,21 +1691,21 @@ __device__ __forceinline__ void split_store_wave_dbm(const Geo& g, const Args& a
     const uint32_t edge = ering[(q + 1 == (uint32_t)T ? 2u : (q & 1)) * 64 + lane];
     cring[(q & 31) * 64 + lane] =
         (code_t)(k_node | (k_fl & (SF_LIVE | SF_DNOLD | SF_ENVC)) | ((edge & (WIDE ? 0x3Fu : 0xFu)) << 4));
-    gbyte* rec = (gbyte*)(OCC ? a.obs_window_occ : a.obs_window) + (q * EN + ag0) * (uint32_t)REC;
+    const uint32_t roff = (q * EN + ag0) * (uint32_t)REC;
 #pragma unroll
     for (int k = 0; k < NRC; ++k)
-      if (k < NRC - 1 || lane + 64 * k < RCH)
-        split_store((__attribute__((address_space(1))) u32x4*)(rec + 16u * (lane + 64 * k)), rv[k]);
+      if (k < NRC - 1 || lane + 64 * k < RCH) split_store_wt16(rrec, roff + 16u * (lane + 64 * k), rv[k]);
     const uint32_t fl = k_fl;
     const uint32_t nzn = (((k_nb & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) >> 7) & 0x01010101u;
     const uint32_t availm = __builtin_amdgcn_udot4(nzn, 0x08040201u, 16u, false);
     const uint32_t ai = q * EN + ag0 + lane;
     const int2 rc = padded_cell_rc(g, (int)k_nc);
-    split_store((__attribute__((address_space(1))) i32x2*)((gbyte*)a.traj_pos + 8u * ai), i32x2{rc.x, rc.y});
-    split_store((gbyte*)a.node + ai, (unsigned char)k_node);
-    split_store((gbyte*)a.edge + ai, (unsigned char)edge);
-    split_store((gbyte*)a.avail + ai, (unsigned char)availm);
-    split_store((gbyte*)a.traj_done + ai, (unsigned char)(fl & SF_DONE));
+    split_store<SplitSt::WT>((unsigned long long*)((unsigned char*)a.traj_pos + 8u * ai),
+                             (unsigned long long)(uint32_t)rc.x | ((unsigned long long)(uint32_t)rc.y << 32));
+    split_store<SplitSt::WT>((unsigned char*)a.node + ai, (unsigned char)k_node);
+    split_store<SplitSt::WT>((unsigned char*)a.edge + ai, (unsigned char)edge);
+    split_store<SplitSt::WT>((unsigned char*)a.avail + ai, (unsigned char)availm);
+    split_store<SplitSt::WT>((unsigned char*)a.traj_done + ai, (unsigned char)(fl & SF_DONE));
     if (ag == LL - 1) {
       const uint32_t ei = q * E + env;
       split_store((__attribute__((address_space(1))) int*)((gbyte*)a.traj_t + 4u * ei), (int)k_t);

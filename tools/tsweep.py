@@ -3,7 +3,10 @@
 from launch-recorded events (mapfx_rollout_timed), median of 7 replays from the same
 state: separates the per-launch fixed cost from the per-step cost.
 
-  python tools/tsweep.py [--T 1,2,4,8,16,20,32,33,48,64] [--config c2]
+  python tools/tsweep.py [--T 1,2,4,8,16,20,32,33,48,64] [--config c2] [--envs E]
+
+--envs overrides the config's env count: the bytes a step writes scale with it, so a knee
+that sits at a fixed number of output bytes moves in T (store policy).
 """
 import argparse
 import os
@@ -19,12 +22,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--T", default="1,2,4,8,16,20,32,33,48,64")
     ap.add_argument("--config", default="c2")
+    ap.add_argument("--envs", type=int, default=0, help="env count (default: the config's)")
     a = ap.parse_args()
     import bench
     import mapfx
     from mapfx import _abi
     from mapfx.maps import synthetic_instances, warehouse_grid
     S, N, E, p, shared = bench.CONFIGS[a.config]
+    E = a.envs or E
+    print("config %s  E = %d  N = %d  %s" % (a.config, E, N, _abi.build_id()), flush=True)
     inst = synthetic_instances(E, S, S, N, p_obstacle=p or 0.0, seed=1,
                                shared_grid=warehouse_grid(S) if shared else None)
     b = mapfx.MapfGridBatch(inst["init_pos"], inst["goals"], bits=inst["bits"], hw=(S, S),
