@@ -135,6 +135,46 @@ int mapfx_partial_step(mapfx_partial_t* h, const mapfx_partial_state* st, const 
 int mapfx_partial_observe(mapfx_partial_t* h, const mapfx_partial_state* st,
                           const mapfx_partial_out* out, void* stream);
 
+/* Device-side scenario draw: new starts and goals of the (masked) envs, the reference's
+ * per-reset re-sampling (:130, __setup_agent :902-929: one of the scen files by
+ * random.randint, then random.sample(lines, N)) with the library's counter-based
+ * streams instead of Python's generator.  Same distribution -- a uniform file, then a
+ * uniform ordered sample of N distinct lines -- but not the same numbers.
+ *
+ * `lines` row j of file k is (start_row, start_col, goal_row, goal_col) of that file's
+ * line j (mapfx.maps.load_scen_table); the kernel trusts the table.  With u64 wrapping
+ * arithmetic, splitmix64 and K_* as in mapfx_action (mapfx.h) / mapfx/rng.py,
+ * gid = cfg.env_offset + e and ep = episode[e]:
+ *
+ *   key(stream, idx) = splitmix64(seed ^ gid*K_ENV ^ ep*K_T ^ idx*K_CELL ^ stream*K_STREAM)
+ *   1. f = ((key(0x500, 0) >> 32) * n_files) >> 32
+ *   2. L = n_lines[f]; L <= N: the env is bad (the reference asserts len(lines) > N)
+ *   3. s_j = (key(0x600, j) & ~0xFFFF) | j for j < L   (distinct: no tie rule)
+ *   4. agent a gets line sorted(s)[a] & 0xFFFF
+ *   5. init_pos[e][a], goal[e][a] from that line; episode[e] = ep + 1
+ *
+ * so an env's instances depend on (seed, gid, ep) only, not on the sharding.
+ * mapfx.rng.scen_draw restates it bit for bit. */
+typedef struct mapfx_partial_scen {
+  uint64_t seed;
+  const int16_t* lines;    /* [F][l_max][4] device */
+  const int32_t* n_lines;  /* [F] device */
+  int32_t n_files, l_max;  /* F >= 1, 1 <= l_max <= 4096 */
+  int32_t* init_pos;       /* [E][N][2] written */
+  int32_t* goal;           /* [E][N][2] written */
+  int32_t* episode;        /* [E] read, incremented for drawn envs */
+  const uint8_t* mask;     /* [E] or NULL */
+  int32_t* err;            /* [1] 0, or 1 + a bad env (first report wins) */
+} mapfx_partial_scen;
+
+/* One launch.  E, N and env_offset are the handle's cfg.  An env with mask[e] == 0 is
+ * neither read nor written; a bad env sets *err and has none of its bytes written,
+ * every other env is drawn.  MAPFX_EINVAL before any launch: a NULL handle, struct,
+ * lines, n_lines, init_pos, goal, episode or err; n_files < 1; l_max outside 1..4096.
+ * Goal-distance tables and pdist are not touched: follow the call with
+ * mapfx_partial_goal_dist on the same mask. */
+int mapfx_partial_draw(mapfx_partial_t* h, const mapfx_partial_scen* sc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1670,6 +1670,117 @@ __global__ void __launch_bounds__(256) pdist_invalidate_kernel(long long total, 
   pdist[i] = PD_NONE;
 }
 
+// ---- device scenario draw (mapfx_partial_draw; definition in mapfx_partial.h, restated
+//      by mapfx/rng.py scen_draw) ----
+// mapfx/rng.py: K_ENV, K_T, K_CELL, K_STREAM and the draw's stream ids
+constexpr uint64_t SK_ENV = 0xD1B54A32D192ED03ull, SK_T = 0xABC98388FB8FAC03ull,
+                   SK_CELL = 0x9E6C63D0676A9A99ull, SK_STREAM = 0xF1357AEA2E62A9C5ull;
+constexpr uint32_t SS_FILE = 0x500u, SS_LINE = 0x600u;
+constexpr int SCEN_LMAX = 4096;       // keys of one env: 32 KB of LDS at most
+constexpr int SCEN_WAVE_LMAX = 1024;  // up to here one wavefront sorts an env's keys
+
+struct SArgs {
+  uint64_t seed;
+  long long env_offset;
+  const int16_t* lines;
+  const int32_t* n_lines;
+  int n_files, l_max;
+  int32_t* init_pos;
+  int32_t* goal;
+  int32_t* episode;
+  const uint8_t* mask;
+  int32_t* err;
+  int N;
+};
+
+__device__ inline uint64_t scen_key(uint64_t base, uint32_t stream, uint32_t idx) {  // splitmix64 (mapfx.hip)
+  uint64_t x = base ^ ((uint64_t)idx * SK_CELL) ^ ((uint64_t)stream * SK_STREAM);
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+
+// compare-exchange of keys[lo] / keys[hi] (lo < hi): the smaller one to lo when `up`
+__device__ __forceinline__ void scen_cmpx(uint64_t* keys, int lo, int hi, bool up) {
+  const uint64_t x = keys[lo], y = keys[hi];
+  if ((x > y) == up) {
+    keys[lo] = y;
+    keys[hi] = x;
+  }
+}
+
+// One workgroup of T threads per env (T = 64 while l_max <= SCEN_WAVE_LMAX, else 256): the L
+// line keys (key & ~0xFFFF) | j of the env's file sit in LDS, padded with ~0 to P = the next
+// power of two (8 P <= 32 KB, the only LDS of the kernel); their N smallest, ascending, end
+// up in keys[0 .. N) and agent a takes the line in the low 16 bits of key a.  The keys are
+// distinct and a pad (low bits 0xFFFF > any j) is above every key, so the order has no ties.
+// Selection, with M = the next power of two of N (2 <= M <= P):
+//   A. a bitonic sort of every chunk of M keys, even chunks ascending, odd ones descending;
+//   B. while more than one chunk is left: of each pair of chunks (ascending, descending;
+//      S keys apart) min(a[i], b[i]) is kept in a -- the M smallest of the 2 M, a bitonic
+//      sequence -- and merged ascending / descending for the next round.  The work halves
+//      with every round; no key above the M smallest of its pair is sorted again.
+// M == P (N > L / 2) is the plain bitonic sort.  Every exit is uniform over the workgroup.
+template <int T>
+__global__ void __launch_bounds__(T) partial_draw_kernel(SArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char scen_lds[];
+  uint64_t* keys = reinterpret_cast<uint64_t*>(scen_lds);
+  const int e = (int)blockIdx.x, tid = (int)threadIdx.x, N = a.N;
+  if (a.mask && !a.mask[e]) return;  // masked out: nothing of the env is read or written
+  const int ep = a.episode[e];
+  const uint64_t base = a.seed ^ ((uint64_t)(a.env_offset + e) * SK_ENV) ^ ((uint64_t)(uint32_t)ep * SK_T);
+  const uint32_t f = (uint32_t)(((scen_key(base, SS_FILE, 0) >> 32) * (uint64_t)(uint32_t)a.n_files) >> 32);
+  const int L = a.n_lines[f];
+  if (L <= N || L > a.l_max) {  // the reference asserts len(lines) > N; (a count past the table's rows: refused too)
+    if (tid == 0) atomicCAS(a.err, 0, e + 1);
+    return;
+  }
+  int P = 2;
+  while (P < L) P <<= 1;  // <= the launch's LDS: P <= next_pow2(l_max)
+  for (int j = tid; j < P; j += T)
+    keys[j] = j < L ? ((scen_key(base, SS_LINE, (uint32_t)j) & ~0xFFFFull) | (uint64_t)j) : ~0ull;
+  __syncthreads();
+  int M = 2, lm = 1;  // lm = log2 M
+  while (M < N) M <<= 1, ++lm;
+  for (int k = 2; k <= M; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int i = tid; i < (P >> 1); i += T) {
+        const int lo = ((i & ~(j - 1)) << 1) | (i & (j - 1));  // i with a 0 inserted at bit log2 j
+        scen_cmpx(keys, lo, lo | j, (lo & k) == 0);
+      }
+      __syncthreads();
+    }
+  }
+  for (int S = M; S < P; S <<= 1) {  // pair p: the chunks at 2 p S (kept) and 2 p S + S
+    const int pairs = P / (2 * S);
+    for (int i = tid; i < pairs * M; i += T) {
+      const int lo = (i >> lm) * 2 * S + (i & (M - 1));
+      scen_cmpx(keys, lo, lo + S, true);
+    }
+    __syncthreads();
+    for (int j = M >> 1; j > 0; j >>= 1) {
+      for (int i = tid; i < pairs * (M >> 1); i += T) {
+        const int p = i >> (lm - 1), o = i & ((M >> 1) - 1);
+        const int lo = p * 2 * S + (((o & ~(j - 1)) << 1) | (o & (j - 1)));
+        scen_cmpx(keys, lo, lo | j, (p & 1) == 0);
+      }
+      __syncthreads();
+    }
+  }
+  const int16_t* tab = a.lines + (long long)f * a.l_max * 4;
+  int32_t* ip = a.init_pos + (long long)e * N * 2;
+  int32_t* gl = a.goal + (long long)e * N * 2;
+  for (int ag = tid; ag < N; ag += T) {
+    const int16_t* row = tab + (int)(keys[ag] & 0xFFFFull) * 4;
+    ip[2 * ag] = row[0];
+    ip[2 * ag + 1] = row[1];
+    gl[2 * ag] = row[2];
+    gl[2 * ag + 1] = row[3];
+  }
+  if (tid == 0) a.episode[e] = ep + 1;  // (every thread read it before the first barrier)
+}
+
 // sqrt(i), i = 0 .. n, with the same device sqrt isqrt_f64 uses (mapfx_partial_create
 // compares it bit for bit with host libm before the kernels may use it)
 __global__ void __launch_bounds__(256) sqrt_probe_kernel(double* out, int n) {
@@ -2118,6 +2229,43 @@ int mapfx_partial_goal_dist(mapfx_partial_t* h, const mapfx_partial_state* st,
   hipLaunchKernelGGL(pdist_invalidate_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, sm, total,
                      g.N, env_mask, st->pdist);
   return check_hip(hipGetLastError(), "pdist_invalidate_kernel launch");
+}
+
+int mapfx_partial_draw(mapfx_partial_t* h, const mapfx_partial_scen* sc, void* stream) {
+  if (!h) return perr(MAPFX_EINVAL, "NULL handle");
+  if (!sc) return perr(MAPFX_EINVAL, "NULL mapfx_partial_scen");
+  if (!sc->lines || !sc->n_lines || !sc->init_pos || !sc->goal || !sc->episode || !sc->err)
+    return perr(MAPFX_EINVAL, "mapfx_partial_scen: lines, n_lines, init_pos, goal, episode and err are required");
+  if (sc->n_files < 1) return perr(MAPFX_EINVAL, "mapfx_partial_scen: n_files must be >= 1");
+  if (sc->l_max < 1 || sc->l_max > SCEN_LMAX)
+    return perr(MAPFX_EINVAL, "mapfx_partial_scen: l_max must be in 1..4096");
+  const PGeo& g = h->geo;
+  if (g.E == 0) return MAPFX_OK;
+  SArgs a;
+  memset(&a, 0, sizeof(a));
+  a.seed = sc->seed;
+  a.env_offset = (long long)h->cfg.env_offset;
+  a.lines = sc->lines;
+  a.n_lines = sc->n_lines;
+  a.n_files = sc->n_files;
+  a.l_max = sc->l_max;
+  a.init_pos = sc->init_pos;
+  a.goal = sc->goal;
+  a.episode = sc->episode;
+  a.mask = sc->mask;
+  a.err = sc->err;
+  a.N = g.N;
+  unsigned P = 2;
+  while (P < (unsigned)sc->l_max) P <<= 1;
+  const hipStream_t sm = (hipStream_t)stream;
+  if (sc->l_max <= SCEN_WAVE_LMAX) {
+    hipLaunchKernelGGL(partial_draw_kernel<64>, dim3((unsigned)g.E), dim3(64), P * 8u, sm, a);
+    mapfx_note_kernel((const void*)partial_draw_kernel<64>);
+  } else {
+    hipLaunchKernelGGL(partial_draw_kernel<256>, dim3((unsigned)g.E), dim3(256), P * 8u, sm, a);
+    mapfx_note_kernel((const void*)partial_draw_kernel<256>);
+  }
+  return check_hip(hipGetLastError(), "partial_draw_kernel launch");
 }
 
 int mapfx_partial_reset(mapfx_partial_t* h, const mapfx_partial_state* st, const uint8_t* env_mask,

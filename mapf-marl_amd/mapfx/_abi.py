@@ -70,6 +70,12 @@ class POut(ctypes.Structure):
     _fields_ = [(k, c_vp) for k in ("reward", "obs", "state", "avail", "err")]
 
 
+class PScen(ctypes.Structure):  # include/mapfx_partial.h mapfx_partial_scen
+    _fields_ = [("seed", c_u64), ("lines", c_vp), ("n_lines", c_vp), ("n_files", c_i32),
+                ("l_max", c_i32), ("init_pos", c_vp), ("goal", c_vp), ("episode", c_vp),
+                ("mask", c_vp), ("err", c_vp)]
+
+
 class QCfg(ctypes.Structure):  # include/mapfx_primal.h
     _fields_ = [(k, c_i32) for k in ("H", "W", "n_agents", "n_envs", "obs_size", "map_shared",
                                      "diagonal")]
@@ -102,7 +108,7 @@ EXPORTS = ("mapfx_abi_version", "mapfx_last_error", "mapfx_build_id", "mapfx_las
            "mapfx_partial_create", "mapfx_partial_destroy", "mapfx_partial_obs_dim",
            "mapfx_partial_goal_dist_elem_size",
            "mapfx_partial_goal_dist", "mapfx_partial_reset", "mapfx_partial_step",
-           "mapfx_partial_observe", "mapfx_primal_create", "mapfx_primal_destroy",
+           "mapfx_partial_observe", "mapfx_partial_draw", "mapfx_primal_create", "mapfx_primal_destroy",
            "mapfx_primal_act", "mapfx_primal_act_timed", "mapfx_primal_observe",
            "mapfx_primal_blocking_count",
            "mapfx_primal_blocking", "mapfx_primal_generate", "mapfx_runner_begin", "mapfx_runner_actions", "mapfx_runner_post",
@@ -164,6 +170,7 @@ def _load():
         "mapfx_partial_reset": (c_i32, [c_vp, P(PState), c_vp, P(POut), c_vp]),
         "mapfx_partial_step": (c_i32, [c_vp, P(PState), c_vp, c_i32, P(POut), c_vp]),
         "mapfx_partial_observe": (c_i32, [c_vp, P(PState), P(POut), c_vp]),
+        "mapfx_partial_draw": (c_i32, [c_vp, P(PScen), c_vp]),
         "mapfx_primal_create": (c_i32, [P(QCfg), P(c_vp)]),
         "mapfx_primal_destroy": (None, [c_vp]),
         "mapfx_primal_act": (c_i32, [c_vp, P(QState), c_vp, c_vp, c_i32, P(QOut), c_vp]),

@@ -65,6 +65,67 @@ def parse_scen_lines(lines):
     return out
 
 
+SCEN_LMAX = 4096  # mapfx_partial_draw sorts at most this many line keys per env
+
+
+def load_scen_table(agents_path: str, H: int, W: int, n_files: int = 25):
+    """The scen files agents_path + "1.scen" .. agents_path + "<n_files>.scen" as the table
+    the device scenario draw (mapfx_partial_draw, MarlPartialBatch.set_scenarios) picks from.
+
+    Returns (lines int16 [F, Lmax, 4], n_lines int32 [F]): row j of file k is line j's
+    (start_row, start_col, goal_row, goal_col) in marl_partial's column order (:922-926,
+    fields 5, 4, 7, 6 of `line.replace('\\t', ',').split(',')`), the header line dropped
+    and rows past a file's length zero.  A missing file is an AssertionError (the reference
+    asserts it exists); the kernel trusts the table, so a coordinate outside [0, H) x [0, W)
+    and Lmax > 4096 are ValueErrors here."""
+    import os
+    files = []
+    for k in range(1, int(n_files) + 1):
+        path = agents_path + str(k) + ".scen"
+        assert os.path.exists(path), "scenario file %s does not exist" % path
+        with open(path) as f:
+            rows = [row.rstrip() for row in f.readlines()][1:]
+        tab = np.zeros((len(rows), 4), dtype=np.int64)
+        for j, row in enumerate(rows):
+            v = row.replace("\t", ",").split(",")
+            tab[j] = (int(v[5]), int(v[4]), int(v[7]), int(v[6]))
+            r, c = tab[j, 0::2], tab[j, 1::2]
+            if r.min() < 0 or r.max() >= H or c.min() < 0 or c.max() >= W:
+                raise ValueError("%s line %d: (row, col) %s / %s outside the %d x %d grid"
+                                 % (path, j + 2, tuple(tab[j, :2]), tuple(tab[j, 2:]), H, W))
+        files.append(tab)
+    lmax = max([len(t) for t in files] + [1])
+    if lmax > SCEN_LMAX:
+        raise ValueError("a scenario file has %d lines; the device draw takes at most %d"
+                         % (lmax, SCEN_LMAX))
+    lines = np.zeros((len(files), lmax, 4), dtype=np.int16)
+    for k, tab in enumerate(files):
+        lines[k, :len(tab)] = tab
+    return lines, np.array([len(t) for t in files], dtype=np.int32)
+
+
+def write_synthetic_scen(agents_path: str, grid: np.ndarray, lengths, seed: int = 1,
+                         map_name: str = "synthetic.map"):
+    """MovingAI-format scen files agents_path + "1.scen" .. for `grid` (0 = free): file k has
+    lengths[k - 1] lines; its starts are the free cells in an order drawn from a splitmix64
+    stream (repeating once a file has more lines than the map free cells, so the lines of a
+    shorter file start on distinct cells), its goals likewise (tests and probes use it where
+    no scen files ship; x = col, y = row as in MovingAI)."""
+    grid = np.asarray(grid)
+    h, w = grid.shape
+    free = np.flatnonzero(grid.reshape(-1) == 0).astype(np.int64)
+    for k, n in enumerate(lengths, start=1):
+        j = np.arange(int(n)) % len(free)
+        order = [np.argsort(rng.cell_keys(seed, [k], len(free), s)[0], kind="stable")
+                 for s in (STREAM_START, STREAM_GOAL)]
+        cells = np.stack([free[order[0]][j], free[order[1]][j]], axis=1)
+        with open(agents_path + str(k) + ".scen", "w") as f:
+            f.write("version 1\n")
+            for j, (s, g) in enumerate(cells):
+                f.write("%d\t%s\t%d\t%d\t%d\t%d\t%d\t%d\t%.8f\n"
+                        % (j // 10, map_name, w, h, s % w, s // w, g % w, g // w, 0.0))
+
+
 def pack_bits(grids: np.ndarray) -> np.ndarray:
     """[E, H, W] (nonzero = obstacle) -> uint8 [E, map_stride(H, W)] device bitmaps."""
     grids = np.asarray(grids)

@@ -134,6 +134,7 @@ class MarlPartialBatch:
         self._obs_out = _abi.POut(reward=None, obs=ptr(self.out["obs"]),
                                   state=ptr(self.out["state"]), avail=ptr(self.out["avail"]),
                                   err=ptr(self.err))
+        self._scen = None   # set_scenarios: the device scenario draw's table and counters
         self.compute_goal_dist()
 
     def __del__(self):
@@ -170,6 +171,40 @@ class MarlPartialBatch:
             self.init_pos[m] = ip[m]
             self.goal[m] = gl[m]
         self.compute_goal_dist(env_mask)
+
+    def set_scenarios(self, lines, n_lines, seed):
+        """Upload the scenario table (maps.load_scen_table) that `redraw` draws from:
+        `episode` [E] int32 counts each env's draws from 0."""
+        lines = np.ascontiguousarray(lines, dtype=np.int16)
+        n_lines = np.ascontiguousarray(n_lines, dtype=np.int32)
+        if lines.ndim != 3 or lines.shape[2] != 4 or n_lines.shape != (lines.shape[0],):
+            raise ValueError("lines must be [F, Lmax, 4] and n_lines [F]")
+        if n_lines.size and (n_lines.min() < 0 or n_lines.max() > lines.shape[1]):
+            raise ValueError("n_lines must be within 0..Lmax")
+        self.scen_lines = torch.as_tensor(lines).to(self.device)
+        self.scen_n_lines = torch.as_tensor(n_lines).to(self.device)
+        self.episode = torch.zeros((self.E,), dtype=torch.int32, device=self.device)
+        # the draw's own report (1 + a bad env), apart from the invalid-action one
+        self.scen_err = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        self._scen = _abi.PScen(seed=int(seed) & 0xFFFFFFFFFFFFFFFF, lines=ptr(self.scen_lines),
+                                n_lines=ptr(self.scen_n_lines), n_files=int(lines.shape[0]),
+                                l_max=int(lines.shape[1]), init_pos=ptr(self.init_pos),
+                                goal=ptr(self.goal), episode=ptr(self.episode), mask=None,
+                                err=ptr(self.scen_err))
+
+    def redraw(self, env_mask=None):
+        """New starts / goals of the masked envs (all if None) drawn on the device
+        (mapfx_partial_draw: a uniform scen file, a uniform ordered sample of its lines --
+        rng.scen_draw names them) and their goal-distance tables.  No host sync, no copy
+        of instances; a file with no more than n_agents lines shows in check_err()."""
+        if self._scen is None:
+            raise RuntimeError("redraw needs set_scenarios(lines, n_lines, seed) first")
+        m = None if env_mask is None else \
+            torch.as_tensor(env_mask, device=self.device).to(torch.uint8).contiguous()
+        self._scen.mask = ptr(m)
+        check(self._call(lib.mapfx_partial_draw, self._h, ctypes.byref(self._scen)),
+              "mapfx_partial_draw")
+        self.compute_goal_dist(m)
 
     def reset(self, env_mask=None):
         """:125-163 for the masked envs (all if None); observations of every env."""
@@ -210,6 +245,12 @@ class MarlPartialBatch:
         return host_flat
 
     def check_err(self):
+        if self._scen is not None:
+            e = int(self.scen_err.item())
+            if e:
+                self.scen_err.zero_()
+                raise AssertionError("scenario file with no more than n_agents lines drawn for "
+                                     "env %d" % (e - 1))
         e = int(self.err.item())
         if e:
             self.err.zero_()

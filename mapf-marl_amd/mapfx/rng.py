@@ -21,6 +21,8 @@ K_STREAM = np.uint64(0xF1357AEA2E62A9C5)
 # mapfx.maps uses 1..3.  The obstacle stream of redraw attempt t is STREAM_GEN_OBST + t,
 # t = 0..32.
 STREAM_GEN_WORLD, STREAM_GEN_OBST, STREAM_GEN_START, STREAM_GEN_GOAL = 0x100, 0x200, 0x300, 0x400
+# Streams of the device MARL_PARTIAL scenario draw (mapfx_partial_draw, csrc/partial.hip)
+STREAM_SCEN_FILE, STREAM_SCEN_LINE = 0x500, 0x600
 
 
 def splitmix64(x):
@@ -58,3 +60,35 @@ def cell_keys(seed, env_ids, n_cells, stream):
     k = (np.uint64(seed) ^ _mul(env, K_ENV) ^ _mul(cell, K_CELL)
          ^ _mul(np.uint64(stream), K_STREAM))
     return splitmix64(k)
+
+
+def scen_draw(seed, env_ids, episodes, n_lines, n_agents):
+    """The device scenario draw of mapfx_partial_draw (include/mapfx_partial.h), restated.
+
+    key(stream, idx) = splitmix64(seed ^ gid*K_ENV ^ ep*K_T ^ idx*K_CELL ^ stream*K_STREAM)
+    per env (global id gid, episode counter ep):
+      f = ((key(STREAM_SCEN_FILE, 0) >> 32) * F) >> 32            a uniform file
+      s_j = (key(STREAM_SCEN_LINE, j) & ~0xFFFF) | j,  j < L = n_lines[f]
+      agent a gets line sorted(s)[a] & 0xFFFF                     a uniform ordered sample
+    (the distribution of random.randint + random.sample, marl_partial.py:902-929).
+    `episodes` is one counter or one per env.  Returns (file int32 [E], line int32
+    [E, n_agents]); an env whose file has no more than n_agents lines (the reference
+    asserts) has a row of -1 (its `file` entry still names the file drawn).
+    """
+    n_lines = np.asarray(n_lines, dtype=np.int64)
+    F, N = int(n_lines.shape[0]), int(n_agents)
+    gid = np.asarray(env_ids, dtype=np.int64).astype(np.uint64)
+    ep = np.broadcast_to(np.asarray(episodes, dtype=np.int64) & 0xFFFFFFFF, gid.shape).astype(np.uint64)
+    base = np.uint64(seed) ^ _mul(gid, K_ENV) ^ _mul(ep, K_T)
+    kf = splitmix64(base ^ _mul(np.uint64(STREAM_SCEN_FILE), K_STREAM))
+    file = (((kf >> np.uint64(32)) * np.uint64(F)) >> np.uint64(32)).astype(np.int32)
+    line = np.full((gid.shape[0], N), -1, dtype=np.int32)
+    sl = _mul(np.uint64(STREAM_SCEN_LINE), K_STREAM)
+    for e in range(gid.shape[0]):
+        L = int(n_lines[file[e]])
+        if L <= N:
+            continue
+        j = np.arange(L, dtype=np.uint64)
+        s = (splitmix64(base[e] ^ _mul(j, K_CELL) ^ sl) & ~np.uint64(0xFFFF)) | j
+        line[e] = (np.sort(s)[:N] & np.uint64(0xFFFF)).astype(np.int32)
+    return file, line

@@ -35,6 +35,10 @@ MARL_PARTIAL_ENV.__setup_agent (:896-920: random.randint(1, 25) then
 random.sample of the scen lines), from a per-env `random.Random(seed + e)` stream
 (the reference's forked workers all share one stream and draw identical instances).
 `instance_fn(episode) -> (starts [B, N, 2], goals [B, N, 2])` overrides the draw.
+`args.runner_device_draw = True` draws on the device instead (MarlPartialBatch.redraw:
+the same distribution from the library's counter-based streams, keyed by args.seed, the
+env id and the run number; run r plays the instances rng.scen_draw(seed, ids, r, ...)
+names), with no host loop and no copy of instances per reset.
 """
 from __future__ import annotations
 
@@ -48,7 +52,7 @@ import torch
 
 from . import _abi
 from ._abi import MAPFX_I8, MAPFX_I32, MAPFX_I64, check, lib, ptr
-from .maps import load_map
+from .maps import load_map, load_scen_table
 from .partial import MarlPartialBatch
 
 _ADT = {torch.int8: MAPFX_I8, torch.int32: MAPFX_I32, torch.int64: MAPFX_I64}
@@ -108,9 +112,27 @@ class ParallelRunner:
         self._rngs = [random.Random(seed + e) for e in range(self.batch_size)]
         self._instance_fn = instance_fn
         self._episode = 0
-        starts, goals = self._draw()
+        # args.runner_device_draw (default False: the host draw above): every reset draws
+        # the envs' scenarios on the device (see the module docstring)
+        self._device_draw = bool(getattr(args, "runner_device_draw", False))
+        if self._device_draw:
+            if instance_fn is not None:
+                raise ValueError("runner_device_draw draws the instances itself: it cannot be "
+                                 "combined with instance_fn")
+            H, W = self.grid.shape
+            lines, n_lines = load_scen_table(self.agents_path, H, W)
+            # placeholder instance from the table's first lines: it consumes no episode
+            # (every env is re-drawn, tables included, by the first reset's redraw)
+            k = int(np.argmax(n_lines > 0))
+            rows = lines[k, np.arange(self.n_agents) % max(int(n_lines[k]), 1)].astype(np.int32)
+            starts = np.repeat(rows[None, :, :2], self.batch_size, axis=0)
+            goals = np.repeat(rows[None, :, 2:], self.batch_size, axis=0)
+        else:
+            starts, goals = self._draw()
         self.env = MarlPartialBatch(starts, goals, grids=self.grid[None], device=self.device, **ea)
         self._loaded = (starts.tobytes(), goals.tobytes())
+        if self._device_draw:
+            self.env.set_scenarios(lines, n_lines, seed=seed)
         self.env_info = {"state_shape": 3, "obs_shape": self.env.obs_dim, "n_actions": 5,
                          "n_agents": self.n_agents, "episode_limit": self.env.episode_limit}
         self.episode_limit = self.env_info["episode_limit"]
@@ -234,11 +256,14 @@ class ParallelRunner:
     def reset(self):
         """:62-76: new batch, every env reset (instances re-drawn, :130), row 0."""
         self.batch = self.new_batch()
-        starts, goals = self._draw()
-        key = (starts.tobytes(), goals.tobytes())
-        if key != self._loaded:           # same instances: the BFS tables still hold
-            self.env.set_agents(starts, goals)
-            self._loaded = key
+        if self._device_draw:
+            self.env.redraw()             # run r draws with the envs' episode counters == r
+        else:
+            starts, goals = self._draw()
+            key = (starts.tobytes(), goals.tobytes())
+            if key != self._loaded:       # same instances: the BFS tables still hold
+                self.env.set_agents(starts, goals)
+                self._loaded = key
         self._episode += 1
         self.env.reset()
         self._erows = self._rows(self.batch)
