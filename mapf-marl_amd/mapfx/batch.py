@@ -315,8 +315,9 @@ class MapfGridBatch:
                                    ("traj_done", traj_done, (T, self.E, self.N), torch.uint8),
                                    ("cell", cell, (T, self.E, self.N), torch.int16),
                                    ("done_bits", done_bits, (T, self.E, nb), torch.uint8)):
+            # (a batch made without a device index has self.device "cuda", its tensors "cuda:k")
             if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() \
-                    or t.device != self.device:
+                    or t.device.type != "cuda" or t.device.index != self._dev_index:
                 raise ValueError("%s must be a contiguous %s %s tensor on %s"
                                  % (name, shape, dt, self.device))
         check(self._call(lib.mapfx_pack_compact, self._h, T, ptr(traj_pos), ptr(traj_done),

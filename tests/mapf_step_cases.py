@@ -670,6 +670,77 @@ def autoreset(ob, term):
     ob.steps[m] = 0
 
 
+def episode(c, b, actions, start=None, refuse=False, count=None):
+    """The oracle's episode of the instance `b` (bits, init_pos, goals of `build`) under
+    `actions` [T, E, N]: the loop `build` itself runs, and what tests/graph_replay_cases.py
+    runs for further episodes of a built case.  Returns (snaps, final, bad): snaps[0] after
+    reset() and snaps[k + 1] after step k (before an autoreset), final = the state after the
+    last step's autoreset, bad = (step, env, agent) of the refused action or None.
+    start: [E, N, 2] positions the episode begins from in place of init_pos, as
+    set_positions leaves them after a reset (done, t and steps zero; an autoreset still
+    returns an env to init_pos).  refuse: write an action outside 0..4 into `actions`
+    (then modified in place) at step min(1, T - 1) for the last live env behind the roles.
+    count = (bumps [T, 5], stats): filled with what the coverage test counts."""
+    N, E, T, H, W = c.N, c.E, c.T, c.H, c.W
+    assert actions.shape == (T, E, N), (actions.shape, (T, E, N))
+    variant = (lambda e: 0) if c.shared else (lambda e: e % VARIANTS)
+    limit = limit_of(c)
+    ob = make_oracle(c, b)
+    if start is not None:
+        ob.pos[...] = start
+    snaps = [_snapshot(ob, c)]
+    bumps, stats = count if count is not None else (None, None)
+    tb = min(1, T - 1)
+    bad = None
+    for t in range(T):
+        if t == tb and refuse:
+            cand = [e for e in range(role_slots(N)[-1][0] + 1, E) if not ob.done[e].all()]
+            assert cand, "no live env for the refused action"
+            be = cand[-1]
+            ba = (0, N // 2, N - 1)[(N + E) % 3]
+            actions[t, be, ba] = BAD[c.act][(N + T) % 3]
+            bad = (t, be, ba)
+        if count is not None:
+            stats["past_done"] += int(ob.done.all(1).sum())
+            if t == T - 1:
+                stats["live_last"] = int((~ob.done.all(1)).sum()) - (1 if bad and bad[0] == t else 0)
+        for e in range(E if count is not None else 0):
+            g = grid_of(H, W, variant(e))
+            if bad and bad[:2] == (t, e):
+                continue
+            cnt = np.zeros((H, W), np.int64)
+            np.add.at(cnt, (ob.pos[e, :, 0], ob.pos[e, :, 1]), 1)
+            for i in range(N):
+                a = int(actions[t, e, i])
+                if ob.done[e, i] or a == 4:
+                    continue
+                r, col = ob.pos[e, i] + DELTAS[a]
+                if not (0 <= r < H and 0 <= col < W):
+                    bumps[t, a] += 1
+                elif g[r, col] != 0 and cnt[r, col] == 0:
+                    bumps[t, 4] += 1
+        a = actions[t]      # 2^32 + 2 must not wrap into 0..4 on its way to the oracle's int32
+        stepped = ob.step(np.where((a < 0) | (a > 4), 7, a).astype(np.int32))
+        assert stepped["bad"] == (1 if bad and bad[0] == t else 0)
+        s = _snapshot(ob, c, stepped)
+        snaps.append(s)
+        if count is not None:
+            stats["node"] = max(stats["node"], int(stepped["node"].sum(1).max()))
+            stats["edge"] = max(stats["edge"], int(stepped["edge"].max()))
+            newly = s["term"].astype(bool) & ~snaps[-2]["term"].astype(bool) if t else s["term"].astype(bool)
+            stats["done_below"] += int((newly & (ob.t < limit)).sum())
+            stats["done_at"] += int((newly & (ob.t >= limit)).sum())
+        if c.autoreset:
+            if count is not None:
+                stats["resets"] += int(s["term"].sum())
+            autoreset(ob, s["term"])
+    final = {k: getattr(ob, k).copy() for k in SNAP_STATE}
+    for v in [x for s in snaps for x in s.values()] + list(final.values()):
+        if isinstance(v, np.ndarray):
+            v.setflags(write=False)
+    return snaps, final, bad
+
+
 @functools.lru_cache(maxsize=None)
 def build(c):
     """A case's maps, instance, actions and the oracle's episode, built once per process and
@@ -685,7 +756,6 @@ def build(c):
     variant = (lambda e: 0) if c.shared else (lambda e: e % VARIANTS)
     nv = 1 if c.shared else E
     grids = np.stack([grid_of(H, W, variant(e)) for e in range(nv)])
-    limit = limit_of(c)
     actions = rng.integers(0, 5, size=(T, E, N)).astype(np.int64)
     init = np.zeros((E, N, 2), np.int32)
     goals = np.zeros((E, N, 2), np.int32)
@@ -745,53 +815,10 @@ def build(c):
         lib = corc.lib()
         actions = np.array([[[lib.orc_action(c.seed, c.env_offset + e, c.t0 + t, i) for i in range(N)]
                              for e in range(E)] for t in range(T)], np.int64)
-    ob = make_oracle(c, b)
-    snaps = [_snapshot(ob, c)]
     bumps = np.zeros((T, 5), np.int64)
     stats = dict(node=0, edge=0, done_below=0, done_at=0, resets=0, past_done=0, live_last=0)
-    tb = min(1, T - 1)
-    bad = None
-    for t in range(T):
-        if t == tb and c.act != "gen":
-            cand = [e for e in range(role_slots(N)[-1][0] + 1, E) if not ob.done[e].all()]
-            assert cand, "no live env for the refused action"
-            be = cand[-1]
-            ba = (0, N // 2, N - 1)[(N + E) % 3]
-            actions[t, be, ba] = BAD[c.act][(N + T) % 3]
-            bad = (t, be, ba)
-        stats["past_done"] += int(ob.done.all(1).sum())
-        if t == T - 1:
-            stats["live_last"] = int((~ob.done.all(1)).sum()) - (1 if bad and bad[0] == t else 0)
-        for e in range(E):
-            g = grid_of(H, W, variant(e))
-            if bad and bad[:2] == (t, e):
-                continue
-            cnt = np.zeros((H, W), np.int64)
-            np.add.at(cnt, (ob.pos[e, :, 0], ob.pos[e, :, 1]), 1)
-            for i in range(N):
-                a = int(actions[t, e, i])
-                if ob.done[e, i] or a == 4:
-                    continue
-                r, col = ob.pos[e, i] + DELTAS[a]
-                if not (0 <= r < H and 0 <= col < W):
-                    bumps[t, a] += 1
-                elif g[r, col] != 0 and cnt[r, col] == 0:
-                    bumps[t, 4] += 1
-        a = actions[t]      # 2^32 + 2 must not wrap into 0..4 on its way to the oracle's int32
-        stepped = ob.step(np.where((a < 0) | (a > 4), 7, a).astype(np.int32))
-        assert stepped["bad"] == (1 if bad and bad[0] == t else 0)
-        s = _snapshot(ob, c, stepped)
-        snaps.append(s)
-        stats["node"] = max(stats["node"], int(stepped["node"].sum(1).max()))
-        stats["edge"] = max(stats["edge"], int(stepped["edge"].max()))
-        newly = s["term"].astype(bool) & ~snaps[-2]["term"].astype(bool) if t else s["term"].astype(bool)
-        stats["done_below"] += int((newly & (ob.t < limit)).sum())
-        stats["done_at"] += int((newly & (ob.t >= limit)).sum())
-        if c.autoreset:
-            stats["resets"] += int(s["term"].sum())
-            autoreset(ob, s["term"])
-    b.update(actions=actions, bad=bad, snaps=snaps, bumps=bumps, stats=stats,
-             final={k: getattr(ob, k).copy() for k in SNAP_STATE})
+    snaps, final, bad = episode(c, b, actions, refuse=c.act != "gen", count=(bumps, stats))
+    b.update(actions=actions, bad=bad, snaps=snaps, bumps=bumps, stats=stats, final=final)
     for v in list(b.values()) + [x for s in snaps for x in s.values()] + list(b["final"].values()):
         if isinstance(v, np.ndarray):
             v.setflags(write=False)

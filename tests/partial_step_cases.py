@@ -414,11 +414,52 @@ def params(c):
     return dict(KW, obs_window=c.win, obs_knn_agents=c.K, episode_limit=limit_of(c))
 
 
-def make_refs(c, b):
-    """Fresh restatement envs of a built case (the goal tables are shared, never modified)."""
+def make_refs(c, b, limit=None):
+    """Fresh restatement envs of a built case (the goal tables are shared, never modified);
+    `limit`: an episode_limit in place of the case's own."""
+    kw = params(c) if limit is None else dict(params(c), episode_limit=limit)
     return [Ref(b["grids"][0 if c.shared else e], b["starts"][e], b["goals"][e],
-                goal_dist=[b["goal_dist"][e, a] for a in range(c.N)], **params(c))
+                goal_dist=[b["goal_dist"][e, a] for a in range(c.N)], **kw)
             for e in range(c.E)]
+
+
+def episode(c, b, actions, count=None, limit=None, resets=None):
+    """The restatement's episode of the instance `b` (grids, starts, goals, goal_dist of
+    `build`) under `actions` [steps, E, N]: the loop `build` itself runs, and what
+    tests/graph_replay_cases.py runs for further episodes of a built case.  Returns the
+    snapshots in call order: after reset(), then after every step.  limit: an episode_limit
+    in place of the case's own.  resets = {k: mask [E]}: reset(env_mask) of the masked envs
+    between step k - 1 and step k, its snapshot (no env's reward is a step's) inserted
+    there.  count = (bumps [steps, 5], stays [steps]): filled for the coverage test."""
+    assert actions.shape[1:] == (c.E, c.N), actions.shape
+    refs = make_refs(c, b, limit)
+    snaps = [snapshot(refs)]
+    for t in range(len(actions)):
+        if resets is not None and t in resets:
+            for e in np.flatnonzero(resets[t]):
+                refs[e].reset()
+            for r in refs:
+                r.last_reward = None
+            snaps.append(snapshot(refs))
+        for e, r in enumerate(refs):
+            occ = r.occ() if count is not None else None
+            for i, a in enumerate(actions[t, e] if count is not None else ()):
+                if r.done[i]:
+                    continue
+                if a == 4:
+                    count[1][t] += bool(r.at_goal[i])
+                    continue
+                cand = (r.pos[i][0] + STEPS[a][0], r.pos[i][1] + STEPS[a][1])
+                if not r._valid(cand):
+                    count[0][t, a] += 1
+                elif r._is_obstacle(occ, cand):
+                    count[0][t, 4] += 1
+            r.step(actions[t, e])
+        snaps.append(snapshot(refs))
+    for s in snaps:
+        for v in s.values():
+            v.setflags(write=False)
+    return snaps
 
 
 def _seed(c):
@@ -471,25 +512,8 @@ def build(c):
                                     for a in range(N)]) for e in range(E)])
     b = {"grids": np.stack([grids[variant(e)] for e in range(1 if c.shared else E)]), "starts": starts, "goals": goals, "goal_dist": goal_dist,
          "actions": actions}
-    refs = make_refs(c, b)
-    snaps = [snapshot(refs)]
     bumps, stays = np.zeros((T, 5), np.int64), np.zeros(T, np.int64)
-    for t in range(T):
-        for e, r in enumerate(refs):
-            occ = r.occ()
-            for i, a in enumerate(actions[t, e]):
-                if r.done[i]:
-                    continue
-                if a == 4:
-                    stays[t] += bool(r.at_goal[i])
-                    continue
-                cand = (r.pos[i][0] + STEPS[a][0], r.pos[i][1] + STEPS[a][1])
-                if not r._valid(cand):
-                    bumps[t, a] += 1
-                elif r._is_obstacle(occ, cand):
-                    bumps[t, 4] += 1
-            r.step(actions[t, e])
-        snaps.append(snapshot(refs))
+    snaps = episode(c, b, actions, count=(bumps, stays))
     b.update(snaps=snaps, bumps=bumps, stays=stays)
     for v in list(b.values()) + [x for s in snaps for x in s.values()]:
         if isinstance(v, np.ndarray):

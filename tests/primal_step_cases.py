@@ -171,8 +171,9 @@ def _crossing(rng, w):
     return found[int(rng.integers(len(found)))] if found else None
 
 
-def drive(rng, wd, K, s=10, diag=False, radius=12):
-    """K calls for the world `wd` (of `world`), chosen call by call on the restatement.
+def drive(rng, wd, K, s=10, diag=False, radius=12, calls=None):
+    """K calls for the world `wd` (of `world`), chosen call by call on the restatement --
+    or, with calls = (ids [K] 1-based, actions [K]), those calls as given (rng unused).
     Returns ids (1-based) and actions [K], the expected outputs of every call -- reward
     and vec as fp64 bit patterns (uint64), done, next_mask, on_goal, valid, obs [K, 4, s, s] --
     pos / past [N, 2] after the last call and after every call (pos_at / past_at), and what
@@ -196,7 +197,10 @@ def drive(rng, wd, K, s=10, diag=False, radius=12):
            "mid": np.zeros(K, bool), "mid_mask": np.zeros(K, bool)}
     for k in range(K):
         call = pending.pop(0) if pending else None
-        u = rng.random()
+        if calls is not None:      # a given script (`episode`): nothing is drawn
+            call, u = (int(calls[0][k]) - 1, int(calls[1][k])), 1.0
+        else:
+            u = rng.random()
         off = [a for a in range(N) if w.pos[a] != w.goals[a]]
         if call is None and u < 0.55 and off:                      # toward the goal
             a = off[int(rng.integers(len(off)))]
@@ -354,12 +358,28 @@ def build(c):
            "starts": np.stack([w["starts"] for w in worlds])[idx],
            "goals": np.stack([w["goals"] for w in worlds])[idx],
            "distinct": n}
+    return _stacked(out, scripts, idx)
+
+
+def _stacked(out, scripts, idx):
     for key in scripts[0]:
         out[key] = np.stack([sc[key] for sc in scripts])[idx]
     for v in out.values():
         if isinstance(v, np.ndarray):
             v.setflags(write=False)
     return out
+
+
+def episode(c, b, calls):
+    """The restatement's outputs of a built case's worlds under calls = (ids [E, K] 1-based,
+    actions [E, K]) in place of the scripts `build` chose: every array of `drive` with a
+    leading E, through `drive` itself (tests/graph_replay_cases.py: further episodes of a
+    built case).  Needs every world its own (pool = 0)."""
+    assert c.pool == 0 and b["distinct"] == c.E
+    ids, acts = calls
+    scripts = [drive(None, {"grid": b["grids"][e], "starts": b["starts"][e], "goals": b["goals"][e]},
+                     ids.shape[1], c.s, c.diag, calls=(ids[e], acts[e])) for e in range(c.E)]
+    return _stacked({}, scripts, np.arange(c.E))
 
 
 # --------------------------------------------------------------------------- dispatch
