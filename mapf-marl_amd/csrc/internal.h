@@ -72,5 +72,63 @@ int mapfx_partial_step_runner(mapfx_partial_t* h, const mapfx_partial_state* st,
                               void* stream);
 #ifdef __cplusplus
 }
+
+// ---- helpers shared by the four translation units: one definition each ----
+#include <hip/hip_ext.h>
+#include <hip/hip_runtime.h>
+#include <stdio.h>
+
+inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
+
+// x / d for 0 <= x < 2^32, 1 <= d < 2^16, with m = magic48(d) = ceil(2^48 / d).
+inline uint64_t magic48(int d) { return ((1ull << 48) + (uint64_t)d - 1) / (uint64_t)d; }
+__device__ inline int fastdiv(int x, uint64_t m) { return (int)(((uint64_t)(uint32_t)x * m) >> 48); }
+
+// the finaliser of every counter-based draw (mapfx/rng.py splitmix64)
+__host__ __device__ inline uint64_t splitmix64(uint64_t x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+
+// the wave's LDS writes before it are visible to its reads after it
+__device__ inline void wave_fence() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// element idx of an int8 / int32 / int64 action buffer; any out-of-range int64 is -1 (invalid)
+__device__ inline int load_action(const void* p, int dtype, long long idx) {
+  if (dtype == MAPFX_I8) return (int)((const int8_t*)p)[idx];
+  if (dtype == MAPFX_I32) return ((const int32_t*)p)[idx];
+  const long long v = ((const int64_t*)p)[idx];
+  return (v < -1 || v > 5) ? -1 : (int)v;
+}
+
+inline int perr(int code, const char* msg) { return mapfx_internal_error(code, msg); }
+
+inline int check_hip(hipError_t e, const char* what) {
+  if (e == hipSuccess) return MAPFX_OK;
+  char buf[512];
+  snprintf(buf, sizeof(buf), "%s: %s", what, hipGetErrorString(e));
+  return perr(MAPFX_EHIP, buf);
+}
+
+// The one launch path.  The Ext form exactly when an event is given (the two are different
+// runtime entry points, and a captured graph records which); NOTED records the kernel for
+// mapfx_last_kernel (and resets mapfx_last_action_path to 0); returns the checked status.
+enum LaunchNote { QUIET, NOTED };
+template <typename... P, typename... A>
+int launch_kernel(void (*fn)(P...), dim3 grid, dim3 block, unsigned lds, hipStream_t stream, hipEvent_t ev0,
+                  hipEvent_t ev1, const char* what, LaunchNote note, const A&... args) {
+  if (ev0 || ev1)
+    hipExtLaunchKernelGGL(fn, grid, block, lds, stream, ev0, ev1, 0, args...);
+  else
+    hipLaunchKernelGGL(fn, grid, block, lds, stream, args...);
+  if (note == NOTED) mapfx_note_kernel((const void*)fn);
+  return check_hip(hipGetLastError(), what);
+}
 #endif
 #endif

@@ -35,12 +35,14 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <type_traits>
 #include <cmath>
 #include <utility>
 #include <new>
 #include <string>
 
+#include "internal.h"
 #include "mapfx.h"
 
 namespace {
@@ -63,23 +65,11 @@ int set_error(int code, const char* fmt, ...) {
   return code;
 }
 
-__host__ __device__ inline uint64_t splitmix64(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-
 __host__ __device__ inline int gen_action(uint64_t seed, int64_t env, int32_t t, int32_t agent) {
   uint64_t k = seed ^ ((uint64_t)env * 0xD1B54A32D192ED03ull) ^
                ((uint64_t)(uint32_t)t * 0xABC98388FB8FAC03ull) ^
                ((uint64_t)(uint32_t)agent * 0x8CB92BA72F3D8DD7ull);
   return (int)(splitmix64(k) % 5ull);
-}
-
-// x / d for 0 <= x < 2^32, 1 <= d < 2^16, with m = ceil(2^48 / d).
-__device__ inline int fastdiv(int x, uint64_t m) {
-  return (int)(((uint64_t)(uint32_t)x * m) >> 48);
 }
 
 // Launch geometry + env constants (uniform per launch).
@@ -213,15 +203,6 @@ struct CellTraits<uint16_t> {
 // (row, col) deltas of actions 0..3 (envs/mapf_gridworld.py:323-330)
 __device__ inline int act_dr(int a) { return a == 0 ? -1 : (a == 1 ? 1 : 0); }
 __device__ inline int act_dc(int a) { return a == 2 ? -1 : (a == 3 ? 1 : 0); }
-
-__device__ inline int load_action(const void* p, int dtype, long long idx) {
-  if (dtype == MAPFX_I8) return (int)((const int8_t*)p)[idx];
-  if (dtype == MAPFX_I32) {
-    return ((const int32_t*)p)[idx];
-  }
-  long long v = ((const int64_t*)p)[idx];
-  return (v < -1 || v > 5) ? -1 : (int)v;  // any out-of-range value is invalid
-}
 
 // Bit (r*W + c) of the env's bitmap staged in LDS.
 __device__ inline uint32_t map_bit(const uint32_t* bits, int idx) {
@@ -1229,12 +1210,6 @@ __device__ inline void build_map_rows_fast(const Geo& g, uint32_t* map32, const 
 __device__ __forceinline__ int xcd_block(int b, int nb) {
   if ((nb & 7) != 0) return b;
   return (b & 7) * (nb >> 3) + (b >> 3);
-}
-
-__device__ inline void wave_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // 4 cells of the c format (one u32) -> obstacle plane bytes (c == 0) and agents
@@ -2618,10 +2593,6 @@ __global__ void pack_compact_kernel(long long total, int N, int W, int nbytes, c
   }
 }
 
-int round_up(int x, int m) { return (x + m - 1) / m * m; }
-
-uint64_t magic48(int d) { return ((1ull << 48) + (uint64_t)d - 1) / (uint64_t)d; }
-
 }  // namespace
 
 struct mapfx_t {
@@ -2673,12 +2644,6 @@ KernelFn pick_kernel(int cell_bytes, int apl, bool roll, int feat) {
                          : pick_kernel_c<uint16_t>(apl, roll, feat);
 }
 
-int check_hip(hipError_t e, const char* what) {
-  if (e != hipSuccess) return set_error(MAPFX_EHIP, "%s: %s", what, hipGetErrorString(e));
-  return MAPFX_OK;
-}
-
-
 constexpr int MAPFX_AB_SHORT_T = 32;
 template <int WIN>
 KernelFn pick_wave_win(bool roll, bool fullw, bool runner, int L, bool split, bool occ, bool short_t) {
@@ -2724,67 +2689,78 @@ KernelFn pick_wave_kernel(int win, bool roll, bool fullw, bool runner, int L, bo
   return nullptr;
 }
 
+// What launch() runs.  pick_wave() leaves fn null when the wave-local fast path does not
+// apply; launch() then fills in the generic kernel.
+struct Pick {
+  KernelFn fn;
+  int blocks, threads, lds;
+  int act_stage;    // Args::act_stage of the launch
+  int action_path;  // mapfx_last_action_path after it
+  const char* what;
+};
+
+// wave-local fast path: N <= 64, no PRIMAL output, window 3/5/7 (or none)
+Pick pick_wave(const Geo& g, const Args& a, bool roll) {
+  Pick p = {};
+  const long long slot_elems = (long long)(roll ? a.T : 1) * g.E * g.N;
+  const bool fits32 = slot_elems * std::max(8, 2 * g.window * g.window) < (1ll << 31) &&
+                      (long long)(roll ? a.T : 1) * g.E * g.H * g.W < (1ll << 31);
+  if (!g.wave_ok || !fits32 || a.obs_primal || a.primal_vec || (a.obs_window && a.obs_window_occ)) return p;
+  const bool fullw = g.N == g.L && g.E % g.EPW == 0;
+  const bool occ = a.obs_window_occ != nullptr;
+  const bool runner = roll && a.reward && a.term && a.node && a.edge && a.avail &&
+                      a.traj_pos && a.traj_done && a.traj_t && (a.obs_window || occ) && !a.obs_full;
+  const uintptr_t al16 = (uintptr_t)a.obs_window | (uintptr_t)a.obs_window_occ | (uintptr_t)a.traj_pos |
+                         (uintptr_t)a.node | (uintptr_t)a.edge | (uintptr_t)a.avail |
+                         (uintptr_t)a.traj_done | (uintptr_t)a.reward | (uintptr_t)a.traj_t;
+  // the split's LDS: M1 (the odd steps' maps of the wave's envs), info + edge rings, the
+  // two store waves' staged records, the reward-code table and ring
+  const int split_lds = g.wv_lds + g.EPW * g.map_env_bytes + SPLIT_DBM_INFO + SPLIT_DBM_EDGE +
+                        2 * 64 * (occ ? g.wlen / 2 : g.wlen) + split_fold_lds(g.L);
+  const bool split = runner && fullw && (g.L == 16 || g.L == 64) && g.wv_split_ok &&
+                     split_lds <= 64 * 1024 && (al16 & 15) == 0;
+  p.fn = pick_wave_kernel((a.obs_window || occ) ? g.window : 0, roll, fullw, runner, g.L, split, occ,
+                          roll && a.T <= MAPFX_AB_SHORT_T);
+  if (!p.fn) return p;
+  // Staged actions (split rollout, int8 buffer, 16-byte aligned, T <= 64): 16 + 64 T
+  // more LDS bytes, taken only while they leave the resident workgroups per CU (160 KB
+  // of LDS) as they are, counted up to the SPLIT_WG_PER_CU the kernel is built for --
+  // C2: 31,168 B, 35,280 B staged at T = 64, four per CU either way
+  const int stage_lds = split ? split_lds + split_stage_lds(a.T) : 0;
+  const auto resident = [](int lds) { return std::min(SPLIT_WG_PER_CU, 160 * 1024 / lds); };
+  p.act_stage = split && a.do_step && !a.use_rng && a.act_dtype == MAPFX_I8 &&
+                        ((uintptr_t)a.actions & 15) == 0 && a.T >= 1 && a.T <= SPLIT_STAGE_MAX_T &&
+                        stage_lds <= 64 * 1024 && resident(stage_lds) == resident(split_lds)
+                    ? 1 : 0;
+  p.blocks = (g.E + g.EPW - 1) / g.EPW;
+  p.threads = split ? 64 * SPLIT_WAVES : 64;
+  p.lds = p.act_stage ? stage_lds : split ? split_lds : g.wv_lds;
+  p.action_path = p.act_stage ? 2 : (split && !a.use_rng) ? 1 : 0;
+  p.what = "mapf_wave_kernel launch";
+  return p;
+}
+
 int launch(mapfx_t* h, Args& a, bool roll, hipStream_t stream, hipEvent_t ev0 = nullptr,
            hipEvent_t ev1 = nullptr) {
   const Geo& g = h->geo;
   if (g.E == 0) return MAPFX_OK;
-  // wave-local fast path: N <= 64, no PRIMAL output, window 3/5/7 (or none)
-  const long long slot_elems = (long long)(roll ? a.T : 1) * g.E * g.N;
-  const bool fits32 = slot_elems * std::max(8, 2 * g.window * g.window) < (1ll << 31) &&
-                      (long long)(roll ? a.T : 1) * g.E * g.H * g.W < (1ll << 31);
-  if (g.wave_ok && fits32 && !a.obs_primal && !a.primal_vec && !(a.obs_window && a.obs_window_occ)) {
-    const bool fullw = g.N == g.L && g.E % g.EPW == 0;
-    const bool occ = a.obs_window_occ != nullptr;
-    const bool runner = roll && a.reward && a.term && a.node && a.edge && a.avail &&
-                        a.traj_pos && a.traj_done && a.traj_t && (a.obs_window || occ) && !a.obs_full;
-    const uintptr_t al16 = (uintptr_t)a.obs_window | (uintptr_t)a.obs_window_occ | (uintptr_t)a.traj_pos |
-                           (uintptr_t)a.node | (uintptr_t)a.edge | (uintptr_t)a.avail |
-                           (uintptr_t)a.traj_done | (uintptr_t)a.reward | (uintptr_t)a.traj_t;
-    // the split's LDS: M1 (the odd steps' maps of the wave's envs), info + edge rings, the
-    // two store waves' staged records, the reward-code table and ring
-    const int split_lds = g.wv_lds + g.EPW * g.map_env_bytes + SPLIT_DBM_INFO + SPLIT_DBM_EDGE +
-                          2 * 64 * (occ ? g.wlen / 2 : g.wlen) + split_fold_lds(g.L);
-    const bool split = runner && fullw && (g.L == 16 || g.L == 64) && g.wv_split_ok &&
-                       split_lds <= 64 * 1024 && (al16 & 15) == 0;
-    KernelFn fn = pick_wave_kernel((a.obs_window || occ) ? g.window : 0, roll, fullw, runner, g.L, split, occ,
-                                   roll && a.T <= MAPFX_AB_SHORT_T);
-    if (fn) {
-      // Staged actions (split rollout, int8 buffer, 16-byte aligned, T <= 64): 16 + 64 T
-      // more LDS bytes, taken only while they leave the resident workgroups per CU (160 KB
-      // of LDS) as they are, counted up to the SPLIT_WG_PER_CU the kernel is built for --
-      // C2: 31,168 B, 35,280 B staged at T = 64, four per CU either way
-      const int stage_lds = split ? split_lds + split_stage_lds(a.T) : 0;
-      const auto resident = [](int lds) { return std::min(SPLIT_WG_PER_CU, 160 * 1024 / lds); };
-      a.act_stage = split && a.do_step && !a.use_rng && a.act_dtype == MAPFX_I8 &&
-                            ((uintptr_t)a.actions & 15) == 0 && a.T >= 1 && a.T <= SPLIT_STAGE_MAX_T &&
-                            stage_lds <= 64 * 1024 && resident(stage_lds) == resident(split_lds)
-                        ? 1 : 0;
-      const int blocks = (g.E + g.EPW - 1) / g.EPW;
-      const dim3 bt(split ? 64 * SPLIT_WAVES : 64);
-      const unsigned ldsb = a.act_stage ? stage_lds : split ? split_lds : g.wv_lds;
-      if (ev0 || ev1)
-        hipExtLaunchKernelGGL(fn, dim3(blocks), bt, ldsb, stream, ev0, ev1, 0, MAPFX_HOT_ARGS(a, g, blocks), a, g);
-      else
-        hipLaunchKernelGGL(fn, dim3(blocks), bt, ldsb, stream, MAPFX_HOT_ARGS(a, g, blocks), a, g);
-      g_last_kernel = (const void*)fn;
-      g_last_action_path = a.act_stage ? 2 : (split && !a.use_rng) ? 1 : 0;
-      return check_hip(hipGetLastError(), "mapf_wave_kernel launch");
-    }
+  Pick p = pick_wave(g, a, roll);
+  if (!p.fn) {
+    int feat = (a.obs_primal || a.primal_vec) ? (FEAT_FULL | FEAT_PRIM) : a.obs_full ? FEAT_FULL : 0;
+    if (roll && feat == 0 && a.reward && a.term && a.node && a.edge && a.avail && a.traj_pos && a.traj_done &&
+        a.traj_t && (a.obs_window || a.obs_window_occ) && !a.reward_f32)
+      feat = FEAT_RUN;  // the runner output set: the per-output tests compile away
+    p.fn = pick_kernel(h->cell_bytes, h->APL, roll, feat);
+    p.blocks = (g.E + g.EPB - 1) / g.EPB;
+    p.threads = g.BT;
+    p.lds = g.gen_lds;
+    p.what = roll ? "mapf_rollout_kernel launch" : "mapf_step_kernel launch";
   }
-  int feat = (a.obs_primal || a.primal_vec) ? (FEAT_FULL | FEAT_PRIM) : a.obs_full ? FEAT_FULL : 0;
-  if (roll && feat == 0 && a.reward && a.term && a.node && a.edge && a.avail && a.traj_pos && a.traj_done &&
-      a.traj_t && (a.obs_window || a.obs_window_occ) && !a.reward_f32)
-    feat = FEAT_RUN;  // the runner output set: the per-output tests compile away
-  KernelFn fn = pick_kernel(h->cell_bytes, h->APL, roll, feat);
-  const int blocks = (g.E + g.EPB - 1) / g.EPB;
-  const int lds = g.gen_lds;
-  if (ev0 || ev1)
-    hipExtLaunchKernelGGL(fn, dim3(blocks), dim3(g.BT), lds, stream, ev0, ev1, 0, MAPFX_HOT_ARGS(a, g, blocks), a, g);
-  else
-    hipLaunchKernelGGL(fn, dim3(blocks), dim3(g.BT), lds, stream, MAPFX_HOT_ARGS(a, g, blocks), a, g);
-  g_last_kernel = (const void*)fn;
-  g_last_action_path = 0;
-  return check_hip(hipGetLastError(), roll ? "mapf_rollout_kernel launch" : "mapf_step_kernel launch");
+  a.act_stage = p.act_stage;
+  const int rc = launch_kernel(p.fn, dim3(p.blocks), dim3(p.threads), p.lds, stream, ev0, ev1, p.what, NOTED,
+                               MAPFX_HOT_ARGS(a, g, p.blocks), a, g);
+  g_last_action_path = p.action_path;
+  return rc;
 }
 
 void fill_state_args(Args& a, const mapfx_state* st) {
@@ -2834,6 +2810,167 @@ int check_out(const mapfx_t* h, const mapfx_out* o) {
     return set_error(MAPFX_EINVAL, "obs_window requested but MAPFX_OBS_WINDOW not in cfg.obs_mode");
   if ((o->obs_primal || o->primal_vec) && !(m & MAPFX_OBS_PRIMAL))
     return set_error(MAPFX_EINVAL, "PRIMAL obs requested but MAPFX_OBS_PRIMAL not in cfg.obs_mode");
+  return MAPFX_OK;
+}
+
+// The launch geometry and LDS layout of a validated configuration: a plain function of the
+// configuration (no HIP call).  cell_bytes: u8 / u16 map cells; apl: the agents-per-lane
+// template argument of the generic kernels.
+int layout(const mapfx_cfg& c, Geo& g, int& cell_bytes, int& apl) {
+  memset(&g, 0, sizeof(g));
+  const int N = c.n_agents;
+  const int es = mapfx_obs_elem_size(N);
+  cell_bytes = es;
+  int L = 1;
+  while (L < N && L < 256) L <<= 1;
+  int lshift = 0;
+  while ((1 << lshift) < L) ++lshift;
+  const int APL = (N + L - 1) / L;
+  apl = APL <= 1 ? 1 : (APL <= 2 ? 2 : 4);
+
+  int P = 1;
+  if (c.obs_mode & MAPFX_OBS_WINDOW) {
+    P = std::max(P, c.window / 2);
+    P = std::max(P, c.window - 1 - c.window / 2);
+  }
+  if (c.obs_mode & MAPFX_OBS_PRIMAL) {
+    P = std::max(P, c.primal_size / 2);
+    P = std::max(P, c.primal_size - 1 - c.primal_size / 2);
+  }
+  const int cpw = 4 / es;  // cells per u32 word
+  const int pl = round_up(P, cpw);
+  // u8 maps (the wave kernels): rows 8-byte aligned for the ds_write_b64 builds, left
+  // and right pads apart.  u16 maps (generic kernel only): the right pad of row r is
+  // the left pad of row r + 1 (pitch - W >= pl >= P cells between two rows' interiors),
+  // plus a tail of pl + P cells after the last row.
+  const int pitch = es == 1 ? round_up(pl + c.W + P, 8 / es) : round_up(c.W + pl, cpw);
+  const int rows = c.H + 2 * P;
+  const int tail = es == 1 ? 0 : pl + P;
+
+  g.H = c.H;
+  g.W = c.W;
+  g.N = N;
+  g.E = c.n_envs;
+  g.env_offset = c.env_offset;
+  g.L = L;
+  g.lshift = lshift;
+  g.P = P;
+  g.pl = pl;
+  g.pitch = pitch;
+  g.rows = rows;
+  g.wpr = pitch / cpw;
+  g.map_words = (rows * pitch + tail + cpw - 1) / cpw;
+  g.m_wpr = magic48(g.wpr);
+  g.m_W = magic48(c.W);
+  g.m_W4 = magic48(std::max(1, c.W / 4));
+  g.m_pitch = magic48(pitch);
+  g.m_pitch24 = (uint32_t)(((1u << 24) + pitch - 1) / pitch);
+  g.bits_words = (int)(((int64_t)c.H * c.W + 31) / 32);
+  g.map_stride = mapfx_map_stride(c.H, c.W);
+  g.map_shared = c.map_shared ? 1 : 0;
+  g.map_env_bytes = round_up(g.map_words * 4, 16);
+  g.bits_env_bytes = round_up(g.bits_words * 4, 16);
+  g.window = c.window;
+  g.wlen = 2 * c.window * c.window;
+  g.psize = c.primal_size;
+  g.obs_mode = c.obs_mode;
+  g.limit = c.episode_limit;
+  g.step_rew = c.step_reward;
+  g.collide_rew = c.collide_reward;
+  g.m_N = magic48(N);
+  g.m_w = magic48(std::max(1, c.window));
+  g.m_ww = magic48(std::max(1, c.window * c.window));
+  g.m_wlen = magic48(std::max(1, g.wlen));
+  const bool prim_arrays = (c.obs_mode & MAPFX_OBS_PRIMAL) != 0;
+
+  if ((int64_t)c.H * c.W >= (1ll << 31) / 8 || g.map_words >= (1 << 30))
+    return set_error(MAPFX_EINVAL, "grid too large");
+
+  // generic block: maps | oldc | newc | [rc | goal: PRIMAL only] | bits == rew | flags
+  auto lds_for = [&](int epb) {  // (64 bits: 256 envs of a 4096 x 4096 map pass 2^31 bytes)
+    long long off = (long long)epb * g.map_env_bytes;
+    off += (prim_arrays ? 4 : 2) * round_up(epb * N * 4, 16);
+    off += std::max(epb * g.bits_env_bytes, round_up(epb * N * 8, 16));
+    off += round_up(epb * 12 * 4, 16);
+    return off;
+  };
+  int EPB = 256 / L;
+  const int LDS_TARGET = 48 * 1024;
+  const int LDS_MAX = 160 * 1024;
+  while (EPB > 1 && lds_for(EPB) > LDS_TARGET) --EPB;
+  if (lds_for(EPB) > LDS_MAX)
+    return set_error(MAPFX_EINVAL, "one env needs %d B of LDS (> %d)", (int)lds_for(1), LDS_MAX);
+  g.EPB = EPB;
+  g.BT = EPB * L;
+  int off = 0;
+  g.off_map = off;
+  off += EPB * g.map_env_bytes;
+  g.off_oldc = off;
+  off += round_up(EPB * N * 4, 16);
+  g.off_newc = off;
+  off += round_up(EPB * N * 4, 16);
+  g.off_rc = g.off_goal = -1;
+  if (prim_arrays) {
+    g.off_rc = off;
+    off += round_up(EPB * N * 4, 16);
+    g.off_goal = off;
+    off += round_up(EPB * N * 4, 16);
+  }
+  g.off_bits = g.off_rew = off;  // the bitmap is dead once the map is built
+  const int rew_bytes = std::max(EPB * g.bits_env_bytes, round_up(EPB * N * 8, 16));
+  off += rew_bytes;
+  g.off_flag = off;
+  off += round_up(EPB * 12 * 4, 16);
+  g.gen_lds = off;
+  // Deferred fold (rollouts with one env per block): the ring of FOLD_R code rows
+  // replaces the fp64 reward row, and is kept only when the block count per CU stays.
+  g.fold_R = 0;
+  g.code_pitch = round_up(2 * N, 16) + 16;  // +16 B: the fold lanes' rows start on other banks
+  g.off_ctab = -1;
+  if (MAPFX_FOLD_R > 0 && EPB == 1 && L >= 64 && std::isfinite(c.step_reward) && std::isfinite(c.collide_reward)) {
+    constexpr int FOLD_R = MAPFX_FOLD_R;
+    const int ring = std::max(rew_bytes, FOLD_R * g.code_pitch);
+    const int lds_f = g.gen_lds - rew_bytes + ring + 32 * 8 + FOLD_R * 4;
+    if (LDS_MAX / lds_f >= LDS_MAX / g.gen_lds) {
+      g.fold_R = FOLD_R;
+      g.off_flag = g.off_rew + ring;
+      g.off_ctab = g.off_flag + round_up(EPB * 12 * 4, 16);
+      g.gen_lds = lds_f;  // step launches share the layout (the ring is unused there)
+    }
+  }
+
+  // wave-local fast path layout (one wavefront = EPW envs)
+  g.wave_ok = 0;
+  if (L <= 64 && es == 1) {
+    const int EPW = 64 / L;
+    g.EPW = EPW;
+    g.wv_bits_env_bytes = round_up(g.bits_words * 4 + 4, 16);
+    g.wv_fast = (c.W <= 64 && g.wpr <= MAPFX_FAST_WPR && (g.wpr & 1) == 0 && pl >= 1 && pl <= 32) ? 1 : 0;
+    int o = 0;
+    g.wv_off_map = o;
+    o += EPW * g.map_env_bytes;
+    g.wv_off_dep = o;
+    o += EPW * g.map_env_bytes;
+    g.wv_off_bits = o;
+    // the fast build reads the bitmap words of its rows straight from global memory (one
+    // wide load per lane staged in LDS measured slower: per-step 5.04 -> 6.25 us, C2 T = 20
+    // 21.7 -> 23.8 us, gpurun_out/r05c)
+    o += g.wv_fast ? 0 : EPW * g.wv_bits_env_bytes;
+    // rew rows: one double per LANE of the env (every lane writes its slot, +0.0 past
+    // N, and the L = 16 fold reads all 16), rounded up to 2 (16 B), +2 doubles so the
+    // envs of a wave start on different banks
+    const int rew_base = std::max((N + 1) / 2 * 2, L);
+    g.wv_rew_row = rew_base + ((rew_base % 16) == 0 ? 2 : 0);
+    g.wv_rew_buf = round_up(EPW * g.wv_rew_row * 8, 16);
+    g.wv_off_rew = o;
+    o += 2 * g.wv_rew_buf;
+    g.wv_lds = o;
+    // the store-wave split's LDS (after the wave layout; only that kernel allocates it)
+    g.wv_off_split = o;
+    g.wv_split_ok = ((L == 16 || L == 64) && (c.window == 3 || c.window == 5 || c.window == 7)) ? 1 : 0;
+    g.wave_ok = (o <= 64 * 1024 && pitch < 256 && g.rows * pitch < 65536) ? 1 : 0;
+  }
+
   return MAPFX_OK;
 }
 
@@ -2914,186 +3051,22 @@ int mapfx_create(const mapfx_cfg* cfg, mapfx_t** out_handle) {
     return set_error(MAPFX_EINVAL, "primal_size %d not in 1..11", c.primal_size);
   if (c.H >= 32768 || c.W >= 32768) return set_error(MAPFX_EINVAL, "grid too large");
 
-  mapfx_t* h = new (std::nothrow) mapfx_t();
+  std::unique_ptr<mapfx_t, void (*)(mapfx_t*)> h(new (std::nothrow) mapfx_t(), mapfx_destroy);
   if (!h) return set_error(MAPFX_ENOMEM, "host allocation failed");
   h->cfg = c;
-  h->pow_lut = nullptr;
-  h->lut_len = 0;
   if (hipGetDevice(&h->device) != hipSuccess) h->device = 0;
+  if (const int rc = layout(c, h->geo, h->cell_bytes, h->APL)) return rc;
 
-  Geo& g = h->geo;
-  memset(&g, 0, sizeof(g));
-  const int N = c.n_agents;
-  const int es = mapfx_obs_elem_size(N);
-  h->cell_bytes = es;
-  int L = 1;
-  while (L < N && L < 256) L <<= 1;
-  int lshift = 0;
-  while ((1 << lshift) < L) ++lshift;
-  const int APL = (N + L - 1) / L;
-  h->APL = APL <= 1 ? 1 : (APL <= 2 ? 2 : 4);
-
-  int P = 1;
-  if (c.obs_mode & MAPFX_OBS_WINDOW) {
-    P = std::max(P, c.window / 2);
-    P = std::max(P, c.window - 1 - c.window / 2);
-  }
-  if (c.obs_mode & MAPFX_OBS_PRIMAL) {
-    P = std::max(P, c.primal_size / 2);
-    P = std::max(P, c.primal_size - 1 - c.primal_size / 2);
-  }
-  const int cpw = 4 / es;  // cells per u32 word
-  const int pl = round_up(P, cpw);
-  // u8 maps (the wave kernels): rows 8-byte aligned for the ds_write_b64 builds, left
-  // and right pads apart.  u16 maps (generic kernel only): the right pad of row r is
-  // the left pad of row r + 1 (pitch - W >= pl >= P cells between two rows' interiors),
-  // plus a tail of pl + P cells after the last row.
-  const int pitch = es == 1 ? round_up(pl + c.W + P, 8 / es) : round_up(c.W + pl, cpw);
-  const int rows = c.H + 2 * P;
-  const int tail = es == 1 ? 0 : pl + P;
-
-  g.H = c.H;
-  g.W = c.W;
-  g.N = N;
-  g.E = c.n_envs;
-  g.env_offset = c.env_offset;
-  g.L = L;
-  g.lshift = lshift;
-  g.P = P;
-  g.pl = pl;
-  g.pitch = pitch;
-  g.rows = rows;
-  g.wpr = pitch / cpw;
-  g.map_words = (rows * pitch + tail + cpw - 1) / cpw;
-  g.m_wpr = magic48(g.wpr);
-  g.m_W = magic48(c.W);
-  g.m_W4 = magic48(std::max(1, c.W / 4));
-  g.m_pitch = magic48(pitch);
-  g.m_pitch24 = (uint32_t)(((1u << 24) + pitch - 1) / pitch);
-  g.bits_words = (int)(((int64_t)c.H * c.W + 31) / 32);
-  g.map_stride = mapfx_map_stride(c.H, c.W);
-  g.map_shared = c.map_shared ? 1 : 0;
-  g.map_env_bytes = round_up(g.map_words * 4, 16);
-  g.bits_env_bytes = round_up(g.bits_words * 4, 16);
-  g.window = c.window;
-  g.wlen = 2 * c.window * c.window;
-  g.psize = c.primal_size;
-  g.obs_mode = c.obs_mode;
-  g.limit = c.episode_limit;
-  g.step_rew = c.step_reward;
-  g.collide_rew = c.collide_reward;
-  g.m_N = magic48(N);
-  g.m_w = magic48(std::max(1, c.window));
-  g.m_ww = magic48(std::max(1, c.window * c.window));
-  g.m_wlen = magic48(std::max(1, g.wlen));
-  const bool prim_arrays = (c.obs_mode & MAPFX_OBS_PRIMAL) != 0;
-
-  if ((int64_t)c.H * c.W >= (1ll << 31) / 8 || g.map_words >= (1 << 30)) {
-    delete h;
-    return set_error(MAPFX_EINVAL, "grid too large");
-  }
-
-  // generic block: maps | oldc | newc | [rc | goal: PRIMAL only] | bits == rew | flags
-  auto lds_for = [&](int epb) {
-    int off = 0;
-    off += epb * g.map_env_bytes;
-    off += (prim_arrays ? 4 : 2) * round_up(epb * N * 4, 16);
-    off += std::max(epb * g.bits_env_bytes, round_up(epb * N * 8, 16));
-    off += round_up(epb * 12 * 4, 16);
-    return off;
-  };
-  int EPB = 256 / L;
-  const int LDS_TARGET = 48 * 1024;
-  const int LDS_MAX = 160 * 1024;
-  while (EPB > 1 && lds_for(EPB) > LDS_TARGET) --EPB;
-  if (lds_for(EPB) > LDS_MAX) {
-    delete h;
-    return set_error(MAPFX_EINVAL, "one env needs %d B of LDS (> %d)", lds_for(1), LDS_MAX);
-  }
-  g.EPB = EPB;
-  g.BT = EPB * L;
-  int off = 0;
-  g.off_map = off;
-  off += EPB * g.map_env_bytes;
-  g.off_oldc = off;
-  off += round_up(EPB * N * 4, 16);
-  g.off_newc = off;
-  off += round_up(EPB * N * 4, 16);
-  g.off_rc = g.off_goal = -1;
-  if (prim_arrays) {
-    g.off_rc = off;
-    off += round_up(EPB * N * 4, 16);
-    g.off_goal = off;
-    off += round_up(EPB * N * 4, 16);
-  }
-  g.off_bits = g.off_rew = off;  // the bitmap is dead once the map is built
-  const int rew_bytes = std::max(EPB * g.bits_env_bytes, round_up(EPB * N * 8, 16));
-  off += rew_bytes;
-  g.off_flag = off;
-  off += round_up(EPB * 12 * 4, 16);
-  g.gen_lds = off;
-  // Deferred fold (rollouts with one env per block): the ring of FOLD_R code rows
-  // replaces the fp64 reward row, and is kept only when the block count per CU stays.
-  g.fold_R = 0;
-  g.code_pitch = round_up(2 * N, 16) + 16;  // +16 B: the fold lanes' rows start on other banks
-  g.off_ctab = -1;
-  if (MAPFX_FOLD_R > 0 && EPB == 1 && L >= 64 && std::isfinite(c.step_reward) && std::isfinite(c.collide_reward)) {
-    constexpr int FOLD_R = MAPFX_FOLD_R;
-    const int ring = std::max(rew_bytes, FOLD_R * g.code_pitch);
-    const int lds_f = g.gen_lds - rew_bytes + ring + 32 * 8 + FOLD_R * 4;
-    if (LDS_MAX / lds_f >= LDS_MAX / g.gen_lds) {
-      g.fold_R = FOLD_R;
-      g.off_flag = g.off_rew + ring;
-      g.off_ctab = g.off_flag + round_up(EPB * 12 * 4, 16);
-      g.gen_lds = lds_f;  // step launches share the layout (the ring is unused there)
-    }
-  }
-
-  // wave-local fast path layout (one wavefront = EPW envs)
-  g.wave_ok = 0;
-  if (L <= 64 && es == 1) {
-    const int EPW = 64 / L;
-    g.EPW = EPW;
-    g.wv_bits_env_bytes = round_up(g.bits_words * 4 + 4, 16);
-    g.wv_fast = (c.W <= 64 && g.wpr <= MAPFX_FAST_WPR && (g.wpr & 1) == 0 && pl >= 1 && pl <= 32) ? 1 : 0;
-    int o = 0;
-    g.wv_off_map = o;
-    o += EPW * g.map_env_bytes;
-    g.wv_off_dep = o;
-    o += EPW * g.map_env_bytes;
-    g.wv_off_bits = o;
-    // the fast build reads the bitmap words of its rows straight from global memory (one
-    // wide load per lane staged in LDS measured slower: per-step 5.04 -> 6.25 us, C2 T = 20
-    // 21.7 -> 23.8 us, gpurun_out/r05c)
-    o += g.wv_fast ? 0 : EPW * g.wv_bits_env_bytes;
-    // rew rows: one double per LANE of the env (every lane writes its slot, +0.0 past
-    // N, and the L = 16 fold reads all 16), rounded up to 2 (16 B), +2 doubles so the
-    // envs of a wave start on different banks
-    const int rew_base = std::max((N + 1) / 2 * 2, L);
-    g.wv_rew_row = rew_base + ((rew_base % 16) == 0 ? 2 : 0);
-    g.wv_rew_buf = round_up(EPW * g.wv_rew_row * 8, 16);
-    g.wv_off_rew = o;
-    o += 2 * g.wv_rew_buf;
-    g.wv_lds = o;
-    // the store-wave split's LDS (after the wave layout; only that kernel allocates it)
-    g.wv_off_split = o;
-    g.wv_split_ok = ((L == 16 || L == 64) && (c.window == 3 || c.window == 5 || c.window == 7)) ? 1 : 0;
-    g.wave_ok = (o <= 64 * 1024 && pitch < 256 && g.rows * pitch < 65536) ? 1 : 0;
-  }
-
-  const int lds_total = g.gen_lds;
+  const int lds_total = h->geo.gen_lds;
   if (lds_total > 64 * 1024) {
     hipError_t e = hipSuccess;
     const int feats[4] = {0, FEAT_FULL, FEAT_FULL | FEAT_PRIM, FEAT_RUN};
     for (int roll = 0; roll < 2 && e == hipSuccess; ++roll)
       for (int fi = 0; fi < 4 && e == hipSuccess; ++fi)
-        e = hipFuncSetAttribute((const void*)pick_kernel(es, h->APL, roll != 0, feats[fi]),
+        e = hipFuncSetAttribute((const void*)pick_kernel(h->cell_bytes, h->APL, roll != 0, feats[fi]),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds_total);
-    if (e != hipSuccess) {
-      delete h;
-      return set_error(MAPFX_EHIP, "hipFuncSetAttribute(LDS=%d): %s", lds_total,
-                       hipGetErrorString(e));
-    }
+    if (e != hipSuccess)
+      return set_error(MAPFX_EHIP, "hipFuncSetAttribute(LDS=%d): %s", lds_total, hipGetErrorString(e));
   }
 
   if (c.obs_mode & MAPFX_OBS_PRIMAL) {
@@ -3101,24 +3074,17 @@ int mapfx_create(const mapfx_cfg* cfg, mapfx_t** out_handle) {
     // tabulate it on the host with the same libm the reference's CPython calls.
     const int n = (c.H - 1) * (c.H - 1) + (c.W - 1) * (c.W - 1) + 1;
     double* lut = (double*)malloc(sizeof(double) * n);
-    if (!lut) {
-      delete h;
-      return set_error(MAPFX_ENOMEM, "host LUT allocation failed");
-    }
+    if (!lut) return set_error(MAPFX_ENOMEM, "host LUT allocation failed");
     // through a volatile pointer: clang would otherwise rewrite pow(x, 0.5) as sqrt(x)
     double (*volatile libm_pow)(double, double) = pow;
     for (int i = 0; i < n; ++i) lut[i] = libm_pow((double)i, 0.5);
     hipError_t e = hipMalloc((void**)&h->pow_lut, sizeof(double) * n);
     if (e == hipSuccess) e = hipMemcpy(h->pow_lut, lut, sizeof(double) * n, hipMemcpyHostToDevice);
     free(lut);
-    if (e != hipSuccess) {
-      if (h->pow_lut) (void)hipFree(h->pow_lut);
-      delete h;
-      return set_error(MAPFX_ENOMEM, "pow LUT: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return set_error(MAPFX_ENOMEM, "pow LUT: %s", hipGetErrorString(e));
     h->lut_len = n;
   }
-  *out_handle = h;
+  *out_handle = h.release();
   return MAPFX_OK;
 }
 
@@ -3151,10 +3117,10 @@ int mapfx_reset(mapfx_t* h, const mapfx_state* st, const uint8_t* env_mask, cons
   const long long total = (long long)g.E * g.N;
   if (total > 0) {
     const int bt = 256;
-    hipLaunchKernelGGL(reset_kernel, dim3((unsigned)((total + bt - 1) / bt)), dim3(bt), 0,
-                       (hipStream_t)stream, g.E, g.N, st->pos, st->init_pos, st->done, st->t,
-                       st->steps, env_mask);
-    if ((rc = check_hip(hipGetLastError(), "reset_kernel launch"))) return rc;
+    rc = launch_kernel(reset_kernel, dim3((unsigned)((total + bt - 1) / bt)), dim3(bt), 0, (hipStream_t)stream,
+                       nullptr, nullptr, "reset_kernel launch", QUIET, g.E, g.N, st->pos, st->init_pos, st->done,
+                       st->t, st->steps, env_mask);
+    if (rc) return rc;
   }
   if (out) return mapfx_observe(h, st, out, stream);
   return MAPFX_OK;
@@ -3206,41 +3172,16 @@ int mapfx_step(mapfx_t* h, const mapfx_state* st, const void* actions, int actio
   return launch(h, a, false, (hipStream_t)stream);
 }
 
-int mapfx_rollout(mapfx_t* h, const mapfx_state* st, int32_t T, const void* actions,
-                  int action_dtype, uint64_t seed, int32_t t0, int32_t autoreset,
-                  const mapfx_out* traj, void* stream) {
+// mapfx_rollout and mapfx_rollout_timed: at least min_T steps (T == 0 is a no-op)
+static int rollout(mapfx_t* h, const mapfx_state* st, int32_t T, int32_t min_T, const void* actions,
+                   int action_dtype, uint64_t seed, int32_t t0, int32_t autoreset, const mapfx_out* traj,
+                   void* start_event, void* stop_event, void* stream) {
   if (!h) return set_error(MAPFX_EINVAL, "NULL handle");
   int rc = check_state(h, st, autoreset != 0);
   if (rc) return rc;
   if ((rc = check_out(h, traj))) return rc;
-  if (T < 0) return set_error(MAPFX_EINVAL, "T < 0");
+  if (T < min_T) return set_error(MAPFX_EINVAL, "T < %d", min_T);
   if (T == 0) return MAPFX_OK;
-  if (actions && (action_dtype < MAPFX_I8 || action_dtype > MAPFX_I64))
-    return set_error(MAPFX_EINVAL, "bad action_dtype %d", action_dtype);
-  Args a;
-  memset(&a, 0, sizeof(a));
-  fill_state_args(a, st);
-  fill_out_args(a, traj);
-  a.actions = actions;
-  a.act_dtype = action_dtype;
-  a.use_rng = actions ? 0 : 1;
-  a.seed = seed;
-  a.t0 = t0;
-  a.T = T;
-  a.autoreset = autoreset ? 1 : 0;
-  a.do_step = 1;
-  a.pow_lut = h->pow_lut;
-  return launch(h, a, true, (hipStream_t)stream);
-}
-
-int mapfx_rollout_timed(mapfx_t* h, const mapfx_state* st, int32_t T, const void* actions,
-                        int action_dtype, uint64_t seed, int32_t t0, int32_t autoreset,
-                        const mapfx_out* traj, void* start_event, void* stop_event, void* stream) {
-  if (!h) return set_error(MAPFX_EINVAL, "NULL handle");
-  int rc = check_state(h, st, autoreset != 0);
-  if (rc) return rc;
-  if ((rc = check_out(h, traj))) return rc;
-  if (T < 1) return set_error(MAPFX_EINVAL, "T < 1");
   if (actions && (action_dtype < MAPFX_I8 || action_dtype > MAPFX_I64))
     return set_error(MAPFX_EINVAL, "bad action_dtype %d", action_dtype);
   Args a;
@@ -3259,6 +3200,18 @@ int mapfx_rollout_timed(mapfx_t* h, const mapfx_state* st, int32_t T, const void
   return launch(h, a, true, (hipStream_t)stream, (hipEvent_t)start_event, (hipEvent_t)stop_event);
 }
 
+int mapfx_rollout(mapfx_t* h, const mapfx_state* st, int32_t T, const void* actions,
+                  int action_dtype, uint64_t seed, int32_t t0, int32_t autoreset,
+                  const mapfx_out* traj, void* stream) {
+  return rollout(h, st, T, 0, actions, action_dtype, seed, t0, autoreset, traj, nullptr, nullptr, stream);
+}
+
+int mapfx_rollout_timed(mapfx_t* h, const mapfx_state* st, int32_t T, const void* actions,
+                        int action_dtype, uint64_t seed, int32_t t0, int32_t autoreset,
+                        const mapfx_out* traj, void* start_event, void* stop_event, void* stream) {
+  return rollout(h, st, T, 1, actions, action_dtype, seed, t0, autoreset, traj, start_event, stop_event, stream);
+}
+
 int mapfx_gen_actions(mapfx_t* h, uint64_t seed, int32_t t0, int32_t T, int8_t* out,
                       void* stream) {
   if (!h) return set_error(MAPFX_EINVAL, "NULL handle");
@@ -3267,10 +3220,9 @@ int mapfx_gen_actions(mapfx_t* h, uint64_t seed, int32_t t0, int32_t T, int8_t* 
   if (total == 0) return MAPFX_OK;
   if (!out) return set_error(MAPFX_EINVAL, "NULL out");
   const int bt = 256;
-  hipLaunchKernelGGL(gen_actions_kernel, dim3((unsigned)((total + bt - 1) / bt)), dim3(bt), 0,
-                     (hipStream_t)stream, total, h->geo.E, h->geo.N, (long long)h->geo.env_offset,
-                     seed, t0, out);
-  return check_hip(hipGetLastError(), "gen_actions_kernel launch");
+  return launch_kernel(gen_actions_kernel, dim3((unsigned)((total + bt - 1) / bt)), dim3(bt), 0,
+                       (hipStream_t)stream, nullptr, nullptr, "gen_actions_kernel launch", QUIET, total,
+                       h->geo.E, h->geo.N, (long long)h->geo.env_offset, seed, t0, out);
 }
 
 int mapfx_pack_compact(mapfx_t* h, int32_t T, const int32_t* traj_pos, const uint8_t* traj_done,
@@ -3284,10 +3236,9 @@ int mapfx_pack_compact(mapfx_t* h, int32_t T, const int32_t* traj_pos, const uin
   if (total == 0) return MAPFX_OK;
   if (!traj_pos || !traj_done || !cell || !done_bits) return set_error(MAPFX_EINVAL, "NULL buffer");
   const int bt = 256;
-  hipLaunchKernelGGL(pack_compact_kernel, dim3((unsigned)((total + bt - 1) / bt)), dim3(bt), 0,
-                     (hipStream_t)stream, total, h->geo.N, h->cfg.W, (h->geo.N + 7) / 8,
-                     (const int2*)traj_pos, traj_done, cell, done_bits);
-  return check_hip(hipGetLastError(), "pack_compact_kernel launch");
+  return launch_kernel(pack_compact_kernel, dim3((unsigned)((total + bt - 1) / bt)), dim3(bt), 0,
+                       (hipStream_t)stream, nullptr, nullptr, "pack_compact_kernel launch", QUIET, total,
+                       h->geo.N, h->cfg.W, (h->geo.N + 7) / 8, (const int2*)traj_pos, traj_done, cell, done_bits);
 }
 
 }  // extern "C"

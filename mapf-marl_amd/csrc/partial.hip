@@ -31,9 +31,9 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <new>
 #include <type_traits>
-#include <vector>
 
 #include "internal.h"
 #include "mapfx.h"
@@ -175,20 +175,13 @@ __device__ __forceinline__ float* obs_env(const PArgs& a, int e, int D, int N) {
   return a.obs ? a.obs + (long long)e * N * D : nullptr;
 }
 
-__device__ inline int load_act(const void* p, int dtype, long long idx) {
-  if (dtype == MAPFX_I8) return (int)((const int8_t*)p)[idx];
-  if (dtype == MAPFX_I32) return ((const int32_t*)p)[idx];
-  const long long v = ((const int64_t*)p)[idx];
-  return (v < -1 || v > 5) ? -1 : (int)v;
-}
-
 // The step's action of agent `ag` of env `env` (oa = env * N + ag).  The runner's fused
 // form (a.ra.act_row): row act_row[env] of the MAC's output, recorded into the
 // EpisodeBatch's actions / actions_onehot rows at ts (parallel_runner.py:104-110 and the
 // OneHot preprocess); an env outside bs stays (it has terminated: nothing of it is
 // recorded again).  Values outside 0..4 come back as -1 (the env is then skipped, :174).
 __device__ inline int step_action(const PArgs& a, int env, int ag, long long oa) {
-  if (!a.ra.act_row) return load_act(a.actions, a.act_dtype, oa);
+  if (!a.ra.act_row) return load_action(a.actions, a.act_dtype, oa);
   const int row = a.ra.act_row[env];
   if (row < 0) return 4;
   const long long i = (long long)row * a.ra.act_row_stride + ag;
@@ -204,12 +197,6 @@ __device__ inline int step_action(const PArgs& a, int env, int ag, long long oa)
     for (int k = 0; k < 5; ++k) oh[k] = v == k ? 1.0f : 0.0f;
   }
   return (v < 0 || v > 4) ? -1 : (int)v;
-}
-
-__device__ inline void wave_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // sqrt(n) of a non-negative integer n <= sq_max in fp64 (math.sqrt of the reference's
@@ -1656,8 +1643,6 @@ __global__ void __launch_bounds__(64 * PARTIAL_MAX_WPB) partial_kernel(PGeo g_, 
 #endif
 }
 
-int round_up(int x, int m) { return (x + m - 1) / m * m; }
-
 // A goal-table rebuild makes the carried distances stale: pdist of every (masked) env
 // becomes PD_NONE, so its next step looks the current and target cells up in the new
 // table (marl_partial.py:228-229 reads _goal_dist afresh every step); pnbr is only read
@@ -1693,12 +1678,8 @@ struct SArgs {
   int N;
 };
 
-__device__ inline uint64_t scen_key(uint64_t base, uint32_t stream, uint32_t idx) {  // splitmix64 (mapfx.hip)
-  uint64_t x = base ^ ((uint64_t)idx * SK_CELL) ^ ((uint64_t)stream * SK_STREAM);
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
+__device__ inline uint64_t scen_key(uint64_t base, uint32_t stream, uint32_t idx) {
+  return splitmix64(base ^ ((uint64_t)idx * SK_CELL) ^ ((uint64_t)stream * SK_STREAM));
 }
 
 // compare-exchange of keys[lo] / keys[hi] (lo < hi): the smaller one to lo when `up`
@@ -1800,17 +1781,6 @@ struct mapfx_partial_t {
 
 namespace {
 
-int perr(int code, const char* msg) { return mapfx_internal_error(code, msg); }
-
-int check_hip(hipError_t e, const char* what) {
-  if (e != hipSuccess) {
-    char buf[256];
-    snprintf(buf, sizeof(buf), "%s: %s", what, hipGetErrorString(e));
-    return perr(MAPFX_EHIP, buf);
-  }
-  return MAPFX_OK;
-}
-
 int check_state(const mapfx_partial_t* h, const mapfx_partial_state* st) {
   if (!st) return perr(MAPFX_EINVAL, "NULL state");
   if (!st->pos || !st->goal || !st->init_pos || !st->steps || !st->at_goal || !st->done ||
@@ -1842,13 +1812,36 @@ void (*pick_wg(int win, int apl))(PGeo, PArgs) {
 
 int wg_apl(const PGeo& g) { return (g.N + WG_THREADS - 1) / WG_THREADS; }
 
-// the fast-path instance: table width (u8 / int16 / run time) x runner fusion
+using PartialFn = void (*)(PGeo, PArgs);
+
+// the fast-path instance: table width (tw: 1 u8 / 2 int16 / 0 run time) x runner fusion
 template <int WIN, int LF>
-void (*pick_fast(bool u8, bool i16, bool run))(PGeo, PArgs) {
-  if (run) return u8 ? partial_kernel<WIN, 5, LF, 1, true> : i16 ? partial_kernel<WIN, 5, LF, 2, true>
-                                                              : partial_kernel<WIN, 5, LF, 0, true>;
-  return u8 ? partial_kernel<WIN, 5, LF, 1, false> : i16 ? partial_kernel<WIN, 5, LF, 2, false>
-                                                         : partial_kernel<WIN, 5, LF, 0, false>;
+PartialFn pick_fast(int tw, bool run) {
+  if (run) return tw == 1 ? partial_kernel<WIN, 5, LF, 1, true> : tw == 2 ? partial_kernel<WIN, 5, LF, 2, true>
+                                                                          : partial_kernel<WIN, 5, LF, 0, true>;
+  return tw == 1 ? partial_kernel<WIN, 5, LF, 1, false> : tw == 2 ? partial_kernel<WIN, 5, LF, 2, false>
+                                                                  : partial_kernel<WIN, 5, LF, 0, false>;
+}
+
+// The one place that names partial_kernel's instances: launch() asks it for the launch's,
+// mapfx_partial_create walks its whole domain (PICK_*) to raise their dynamic-LDS limit.
+// nullptr: no instance has this window.
+constexpr int PICK_WIN[] = {0, 1, 3, 5, 7, 9}, PICK_K[] = {5, 0}, PICK_L[] = {8, 16, 32, 64}, PICK_TW[] = {0, 1, 2};
+PartialFn pick(int win, int K, int L, int tw, bool run) {
+  if (K == 5 && win == 5 && L == 16) return pick_fast<5, 16>(tw, run);
+  if (K == 5 && win == 5 && L == 8) return pick_fast<5, 8>(tw, run);
+  if (K == 5 && win == 5 && L == 32) return pick_fast<5, 32>(tw, run);
+  if (K == 5 && win == 3 && L == 16) return pick_fast<3, 16>(tw, run);
+  if (K == 5 && win == 7 && L == 16) return pick_fast<7, 16>(tw, run);
+  switch (win) {
+    case 0: return partial_kernel<0, 0, 0>;
+    case 1: return partial_kernel<1, 0, 0>;
+    case 3: return partial_kernel<3, 0, 0>;
+    case 5: return partial_kernel<5, 0, 0>;
+    case 7: return partial_kernel<7, 0, 0>;
+    case 9: return partial_kernel<9, 0, 0>;
+  }
+  return nullptr;
 }
 
 int launch(mapfx_partial_t* h, PArgs& a, void* stream) {
@@ -1856,37 +1849,19 @@ int launch(mapfx_partial_t* h, PArgs& a, void* stream) {
   if (g.E == 0) return MAPFX_OK;
   a.bonus_lut = h->bonus_lut;
   if (h->no_nbcarry) a.pnbr = nullptr;
-  if (g.big) {  // N > 64 or a side > 256: one workgroup per env, map in HBM
-    void (*fn)(PGeo, PArgs) = pick_wg(g.win, wg_apl(g));
-    if (!fn) return perr(MAPFX_EINVAL, "obs_window must be one of 0, 1, 3, 5, 7, 9");
-    hipLaunchKernelGGL(fn, dim3(g.E), dim3(WG_THREADS), g.wg_lds, (hipStream_t)stream, g, a);
-    mapfx_note_kernel((const void*)fn);
-    return check_hip(hipGetLastError(), "partial_wg_kernel launch");
-  }
-  const int blocks = (g.E + g.EPW - 1) / g.EPW;
-  void (*fn)(PGeo, PArgs) = nullptr;
-  const bool u8 = g.gd8 != 0, i16 = !g.gd8 && !g.gd32;  // the table width, as a template argument
   // the runner's fused step, or observation rows to an EpisodeBatch time row
   const bool run = a.ra.act_row != nullptr || a.ra.alive != nullptr || a.obs_rows != nullptr;
-  if (g.K == 5 && g.win == 5 && g.L == 16) fn = pick_fast<5, 16>(u8, i16, run);
-  else if (g.K == 5 && g.win == 5 && g.L == 8) fn = pick_fast<5, 8>(u8, i16, run);
-  else if (g.K == 5 && g.win == 5 && g.L == 32) fn = pick_fast<5, 32>(u8, i16, run);
-  else if (g.K == 5 && g.win == 3 && g.L == 16) fn = pick_fast<3, 16>(u8, i16, run);
-  else if (g.K == 5 && g.win == 7 && g.L == 16) fn = pick_fast<7, 16>(u8, i16, run);
-  else switch (g.win) {
-      case 0: fn = partial_kernel<0, 0, 0>; break;
-      case 1: fn = partial_kernel<1, 0, 0>; break;
-      case 3: fn = partial_kernel<3, 0, 0>; break;
-      case 5: fn = partial_kernel<5, 0, 0>; break;
-      case 7: fn = partial_kernel<7, 0, 0>; break;
-      case 9: fn = partial_kernel<9, 0, 0>; break;
-      default: return perr(MAPFX_EINVAL, "obs_window must be one of 0, 1, 3, 5, 7, 9");
-    }
+  // N > 64 or a side > 256: one workgroup per env, map in HBM
+  const PartialFn fn = g.big ? pick_wg(g.win, wg_apl(g)) : pick(g.win, g.K, g.L, g.gd8 ? 1 : g.gd32 ? 0 : 2, run);
+  if (!fn) return perr(MAPFX_EINVAL, "obs_window must be one of 0, 1, 3, 5, 7, 9");
+  if (g.big)
+    return launch_kernel(fn, dim3(g.E), dim3(WG_THREADS), g.wg_lds, (hipStream_t)stream, nullptr, nullptr,
+                         "partial_wg_kernel launch", NOTED, g, a);
+  const int blocks = (g.E + g.EPW - 1) / g.EPW;
   // (+ one workgroup for the runner's fused compaction, partial_kernel's first block)
   const int nblk = (blocks + g.wpb - 1) / g.wpb + (run && a.ra.cmp_bs ? 1 : 0);
-  hipLaunchKernelGGL(fn, dim3(nblk), dim3(64 * g.wpb), g.lds * g.wpb, (hipStream_t)stream, g, a);
-  mapfx_note_kernel((const void*)fn);
-  return check_hip(hipGetLastError(), "partial_kernel launch");
+  return launch_kernel(fn, dim3(nblk), dim3(64 * g.wpb), g.lds * g.wpb, (hipStream_t)stream, nullptr, nullptr,
+                       "partial_kernel launch", NOTED, g, a);
 }
 
 void fill_state(PArgs& a, const mapfx_partial_state* st) {
@@ -1917,32 +1892,17 @@ void fill_out(PArgs& a, const mapfx_partial_out* o) {
   a.err = o->err;
 }
 
-}  // namespace
+// the goal-distance BFS instance `fn` (tables of DT), recorded for mapfx_last_kernel
+template <typename DT>
+int launch_bfs(void (*fn)(PGeo, const uint8_t*, const int32_t*, const uint8_t*, DT*), int threads, int lds,
+               const PGeo& g, const mapfx_partial_state* st, const uint8_t* env_mask, hipStream_t sm) {
+  return launch_kernel(fn, dim3((unsigned)(g.E * g.N)), dim3(threads), lds, sm, nullptr, nullptr,
+                       "partial_bfs_kernel launch", NOTED, g, st->map_bits, st->goal, env_mask, (DT*)st->goal_dist);
+}
 
-extern "C" {
-
-int mapfx_partial_create(const mapfx_partial_cfg* cfg, mapfx_partial_t** out) {
-  if (!cfg || !out) return perr(MAPFX_EINVAL, "NULL argument");
-  *out = nullptr;
-  const mapfx_partial_cfg& c = *cfg;
-  if (c.H < 1 || c.W < 1 || c.H > HUGE_THREADS * 2 || c.W > 64 * HUGE_WORDS)
-    return perr(MAPFX_EINVAL, "MARL_PARTIAL path supports 1 <= H <= 1024, 1 <= W <= 1536");
-  if (c.n_agents < 1 || c.n_agents > 4 * WG_THREADS) return perr(MAPFX_EINVAL, "n_agents must be in 1..1024");
-  if (c.n_envs < 0) return perr(MAPFX_EINVAL, "n_envs < 0");
-  if (c.episode_limit < 1) return perr(MAPFX_EINVAL, "episode_limit must be >= 1");
-  if (c.obs_knn_agents < 1) return perr(MAPFX_EINVAL, "obs_knn_agents must be >= 1");
-  if (c.obs_window < 0 || c.obs_window > 9 || (c.obs_window > 0 && !(c.obs_window & 1)))
-    return perr(MAPFX_EINVAL, "obs_window must be 0 or odd <= 9");
-  mapfx_partial_t* h = new (std::nothrow) mapfx_partial_t();
-  if (!h) return perr(MAPFX_ENOMEM, "host allocation failed");
-  h->cfg = c;
-  h->bonus_lut = nullptr;
-  h->no_nbcarry = 0;
-#ifdef MAPFX_PARTIAL_DIAG_ENV  // A/B knobs read from the environment: diagnostic builds only
-  if (const char* ev = getenv("MAPFX_PARTIAL_NBCARRY")) h->no_nbcarry = atoi(ev) == 0;
-#endif
-  if (hipGetDevice(&h->device) != hipSuccess) h->device = 0;
-  PGeo& g = h->geo;
+// The launch geometry and LDS layout of a validated configuration: a plain function of the
+// configuration (no HIP call).  Returns the refusal's message, nullptr when there is none.
+const char* layout(const mapfx_partial_cfg& c, PGeo& g) {
   memset(&g, 0, sizeof(g));
   g.H = c.H;
   g.W = c.W;
@@ -1984,11 +1944,15 @@ int mapfx_partial_create(const mapfx_partial_cfg* cfg, mapfx_partial_t** out) {
   g.nc_rew = c.node_collide_reward;
   g.ec_rew = c.edge_collide_reward;
   g.env_rew = c.env_collide_reward;
+  // the LUT sizes: sqrt(0 .. sq_max), the completion bonus at t = 0 .. bonus_len - 1
+  const int S = std::max(c.H, c.W);
+  g.sq_max = 2 * (S - 1) * (S - 1);
+  g.bonus_len = c.episode_limit + BONUS_EXTRA;
   const int per_env = 2 * g.map_env_bytes + g.bits_env_bytes + g.feat_env_bytes + g.pos_env_bytes +
                       g.rew_env_bytes;
   // envs per wave: as many as fit 64 KB of LDS; one env may take up to the CU's
-  // 160 KB (maps up to 256 x 256), with the dynamic-LDS limit raised below (the
-  // workgroup path keeps no map in LDS)
+  // 160 KB (maps up to 256 x 256), with the dynamic-LDS limit raised by mapfx_partial_create
+  // (the workgroup path keeps no map in LDS)
   int EPW = g.big ? 1 : 64 / L;
   while (EPW > 1 && EPW * per_env > 64 * 1024) --EPW;
 #ifdef MAPFX_PARTIAL_DIAG_ENV
@@ -1997,30 +1961,7 @@ int mapfx_partial_create(const mapfx_partial_cfg* cfg, mapfx_partial_t** out) {
     if (v >= 1 && v < EPW) EPW = v;
   }
 #endif
-  if (!g.big && EPW * per_env > 160 * 1024) {
-    delete h;
-    return perr(MAPFX_EINVAL, "one env needs more than 160 KB of LDS (map too large)");
-  }
-  if (g.big && g.huge_lds > 0) {
-    // the frontier rows plus the kernel's own static LDS (__syncthreads_or's scratch)
-    hipFuncAttributes fa;
-    memset(&fa, 0, sizeof fa);
-    (void)hipFuncGetAttributes(&fa, g.gd32 ? (const void*)partial_bfs_huge_kernel<int32_t>
-                                           : (const void*)partial_bfs_huge_kernel<int16_t>);
-    if (g.huge_lds + (int)fa.sharedSizeBytes > 160 * 1024) {
-      char msg[240];
-      snprintf(msg, sizeof msg,
-               "MARL_PARTIAL: the %d x %d map's BFS frontier needs H * ceil(W / 64) * 8 = %d B of "
-               "LDS (+ %d B static; the CU has 160 KB: H * ceil(W / 64) must stay below ~20470)",
-               c.H, c.W, g.huge_lds, (int)fa.sharedSizeBytes);
-      delete h;
-      return perr(MAPFX_EINVAL, msg);
-    }
-  }
-  if (g.big && g.wg_lds > 160 * 1024) {
-    delete h;
-    return perr(MAPFX_EINVAL, "MARL_PARTIAL: the workgroup path needs more than 160 KB of LDS");
-  }
+  if (!g.big && EPW * per_env > 160 * 1024) return "one env needs more than 160 KB of LDS (map too large)";
   g.EPW = EPW;
   int off = 0;
   g.off_map = off; off += EPW * g.map_env_bytes;
@@ -2032,10 +1973,9 @@ int mapfx_partial_create(const mapfx_partial_cfg* cfg, mapfx_partial_t** out) {
   // the K-nearest rows' distances sqrt(0 .. sq_max) as float32, one table per wave filled
   // while the state loads are in flight (small maps: sq_max < 512, i.e. sides up to 16)
   g.off_sqrt = -1;
-  const long long sq_max_ = 2ll * (std::max(c.H, c.W) - 1) * (std::max(c.H, c.W) - 1);  // = g.sq_max below
-  if (sq_max_ < 512) {
+  if (g.sq_max < 512) {
     g.off_sqrt = off;
-    off += round_up((int)(sq_max_ + 1) * 4, 16);
+    off += round_up((g.sq_max + 1) * 4, 16);
   }
   // the fast observation path's staging images (one env's rows + 16 bytes of alignment
   // slack each) for a group of 64 lanes (the whole wave) or 32 (each half in turn),
@@ -2069,98 +2009,111 @@ int mapfx_partial_create(const mapfx_partial_cfg* cfg, mapfx_partial_t** out) {
 #endif
     while (g.wpb > 1 && g.wpb * g.lds > 160 * 1024) --g.wpb;
   }
+  return nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mapfx_partial_create(const mapfx_partial_cfg* cfg, mapfx_partial_t** out) {
+  if (!cfg || !out) return perr(MAPFX_EINVAL, "NULL argument");
+  *out = nullptr;
+  const mapfx_partial_cfg& c = *cfg;
+  if (c.H < 1 || c.W < 1 || c.H > HUGE_THREADS * 2 || c.W > 64 * HUGE_WORDS)
+    return perr(MAPFX_EINVAL, "MARL_PARTIAL path supports 1 <= H <= 1024, 1 <= W <= 1536");
+  if (c.n_agents < 1 || c.n_agents > 4 * WG_THREADS) return perr(MAPFX_EINVAL, "n_agents must be in 1..1024");
+  if (c.n_envs < 0) return perr(MAPFX_EINVAL, "n_envs < 0");
+  if (c.episode_limit < 1) return perr(MAPFX_EINVAL, "episode_limit must be >= 1");
+  if (c.obs_knn_agents < 1) return perr(MAPFX_EINVAL, "obs_knn_agents must be >= 1");
+  if (c.obs_window < 0 || c.obs_window > 9 || (c.obs_window > 0 && !(c.obs_window & 1)))
+    return perr(MAPFX_EINVAL, "obs_window must be 0 or odd <= 9");
+  std::unique_ptr<mapfx_partial_t, void (*)(mapfx_partial_t*)> h(new (std::nothrow) mapfx_partial_t(),
+                                                                 mapfx_partial_destroy);
+  if (!h) return perr(MAPFX_ENOMEM, "host allocation failed");
+  h->cfg = c;
+#ifdef MAPFX_PARTIAL_DIAG_ENV  // A/B knobs read from the environment: diagnostic builds only
+  if (const char* ev = getenv("MAPFX_PARTIAL_NBCARRY")) h->no_nbcarry = atoi(ev) == 0;
+#endif
+  if (hipGetDevice(&h->device) != hipSuccess) h->device = 0;
+  PGeo& g = h->geo;
+  if (const char* msg = layout(c, g)) return perr(MAPFX_EINVAL, msg);
+  const void* huge_bfs = g.gd32 ? (const void*)partial_bfs_huge_kernel<int32_t>
+                                : (const void*)partial_bfs_huge_kernel<int16_t>;
+  if (g.big && g.huge_lds > 0) {
+    // the frontier rows plus the kernel's own static LDS (__syncthreads_or's scratch)
+    hipFuncAttributes fa;
+    memset(&fa, 0, sizeof fa);
+    (void)hipFuncGetAttributes(&fa, huge_bfs);
+    if (g.huge_lds + (int)fa.sharedSizeBytes > 160 * 1024) {
+      char msg[240];
+      snprintf(msg, sizeof msg,
+               "MARL_PARTIAL: the %d x %d map's BFS frontier needs H * ceil(W / 64) * 8 = %d B of "
+               "LDS (+ %d B static; the CU has 160 KB: H * ceil(W / 64) must stay below ~20470)",
+               c.H, c.W, g.huge_lds, (int)fa.sharedSizeBytes);
+      return perr(MAPFX_EINVAL, msg);
+    }
+  }
+  if (g.big && g.wg_lds > 160 * 1024)
+    return perr(MAPFX_EINVAL, "MARL_PARTIAL: the workgroup path needs more than 160 KB of LDS");
+  // device resources: dynamic-LDS limits above 64 KB, then the LUT and the sqrt check
+  int rc = MAPFX_OK;
   if (g.big) {
-    int rc0 = MAPFX_OK;
     if (g.wg_lds > 64 * 1024)
-      rc0 = check_hip(hipFuncSetAttribute((const void*)pick_wg(g.win, wg_apl(g)),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, g.wg_lds),
-                      "hipFuncSetAttribute(partial_wg_kernel LDS)");
-    if (!rc0 && g.huge_lds > 64 * 1024 &&
-        hipFuncSetAttribute(g.gd32 ? (const void*)partial_bfs_huge_kernel<int32_t>
-                                   : (const void*)partial_bfs_huge_kernel<int16_t>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, g.huge_lds) != hipSuccess) {
+      rc = check_hip(hipFuncSetAttribute((const void*)pick_wg(g.win, wg_apl(g)),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, g.wg_lds),
+                     "hipFuncSetAttribute(partial_wg_kernel LDS)");
+    if (!rc && g.huge_lds > 64 * 1024 &&
+        hipFuncSetAttribute(huge_bfs, hipFuncAttributeMaxDynamicSharedMemorySize, g.huge_lds) != hipSuccess) {
       (void)hipGetLastError();
       char msg[200];
       snprintf(msg, sizeof msg,
                "MARL_PARTIAL: the %d x %d map's BFS frontier (H * ceil(W / 64) * 8 = %d B) exceeds "
                "the LDS a workgroup may allocate", c.H, c.W, g.huge_lds);
-      rc0 = perr(MAPFX_EINVAL, msg);
-    }
-    if (rc0) {
-      delete h;
-      return rc0;
+      rc = perr(MAPFX_EINVAL, msg);
     }
   } else if (g.lds * g.wpb > 64 * 1024) {
-    int rc0 = MAPFX_OK;
-    std::vector<void (*)(PGeo, PArgs)> fns = {partial_kernel<0, 0, 0>, partial_kernel<1, 0, 0>,
-                                              partial_kernel<3, 0, 0>, partial_kernel<5, 0, 0>,
-                                              partial_kernel<7, 0, 0>, partial_kernel<9, 0, 0>};
-    for (int t = 0; t < 6; ++t) {  // every fast instance
-      const bool u8 = t % 3 == 0, i16 = t % 3 == 1, run = t >= 3;
-      fns.push_back(pick_fast<5, 16>(u8, i16, run));
-      fns.push_back(pick_fast<5, 8>(u8, i16, run));
-      fns.push_back(pick_fast<5, 32>(u8, i16, run));
-      fns.push_back(pick_fast<3, 16>(u8, i16, run));
-      fns.push_back(pick_fast<7, 16>(u8, i16, run));
-    }
-    for (auto fn : fns)
-      if (!rc0) rc0 = check_hip(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                    g.lds * g.wpb),
-                                "hipFuncSetAttribute(partial_kernel LDS)");
-    if (rc0) {
-      delete h;
-      return rc0;
-    }
+    for (int win : PICK_WIN)  // every instance pick() can return
+      for (int K : PICK_K)
+        for (int L : PICK_L)
+          for (int tw : PICK_TW)
+            for (int run = 0; run < 2 && !rc; ++run)
+              rc = check_hip(hipFuncSetAttribute((const void*)pick(win, K, L, tw, run != 0),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, g.lds * g.wpb),
+                             "hipFuncSetAttribute(partial_kernel LDS)");
   }
+  if (rc) return rc;
   {  // the map build's multiply-high division (partial_kernel) must be exact on its range
     const unsigned long long nw = (unsigned long long)g.rows * g.wpr;
     for (unsigned long long wi = 0; wi < nw; ++wi)
-      if (((wi * g.m_wpr) >> 32) != wi / (unsigned long long)g.wpr) {
-        delete h;
+      if (((wi * g.m_wpr) >> 32) != wi / (unsigned long long)g.wpr)
         return perr(MAPFX_EINVAL, "MARL_PARTIAL: map too large for the padded-map word index");
-      }
   }
   // the completion-bonus LUT from host libm (float ** int is correctly rounded there) and
   // the sqrt reference values the device sqrt is checked against
-  const int S = std::max(c.H, c.W);
-  g.sq_max = 2 * (S - 1) * (S - 1);
-  g.bonus_len = c.episode_limit + BONUS_EXTRA;
-  double* sq = (double*)malloc(sizeof(double) * (g.sq_max + 1));
-  double* bo = (double*)malloc(sizeof(double) * g.bonus_len);
-  if (!sq || !bo) {
-    free(sq);
-    free(bo);
-    delete h;
-    return perr(MAPFX_ENOMEM, "host allocation failed");
-  }
+  const size_t nsq = (size_t)g.sq_max + 1;
+  const std::unique_ptr<double[]> sq(new (std::nothrow) double[nsq]), bo(new (std::nothrow) double[g.bonus_len]),
+      back(new (std::nothrow) double[nsq]);
+  if (!sq || !bo || !back) return perr(MAPFX_ENOMEM, "host allocation failed");
   double (*volatile libm_sqrt)(double) = sqrt;
   double (*volatile libm_pow)(double, double) = pow;
   for (int i = 0; i <= g.sq_max; ++i) sq[i] = libm_sqrt((double)i);
   for (int t = 0; t < g.bonus_len; ++t)  // (complete / (gamma ** (limit - t))) * fac  (:292)
     bo[t] = (c.complete_reward / libm_pow(c.gamma, (double)(c.episode_limit - t))) * c.complete_fac;
-  int rc = check_hip(hipMalloc(&h->bonus_lut, sizeof(double) * g.bonus_len), "hipMalloc");
-  if (!rc) rc = check_hip(hipMemcpy(h->bonus_lut, bo, sizeof(double) * g.bonus_len, hipMemcpyHostToDevice), "hipMemcpy");
+  rc = check_hip(hipMalloc(&h->bonus_lut, sizeof(double) * g.bonus_len), "hipMalloc");
+  if (!rc) rc = check_hip(hipMemcpy(h->bonus_lut, bo.get(), sizeof(double) * g.bonus_len, hipMemcpyHostToDevice), "hipMemcpy");
   // the kernels' sqrt (isqrt_f64) must equal host libm on every argument they can use
   double* probe = nullptr;
-  double* back = rc ? nullptr : (double*)malloc(sizeof(double) * (g.sq_max + 1));
-  if (!rc && !back) rc = perr(MAPFX_ENOMEM, "host allocation failed");
-  if (!rc) rc = check_hip(hipMalloc(&probe, sizeof(double) * (g.sq_max + 1)), "hipMalloc");
-  if (!rc) {
-    hipLaunchKernelGGL(sqrt_probe_kernel, dim3((unsigned)(g.sq_max / 256 + 1)), dim3(256), 0, 0, probe, g.sq_max);
-    rc = check_hip(hipGetLastError(), "sqrt_probe_kernel launch");
-  }
-  if (!rc) rc = check_hip(hipMemcpy(back, probe, sizeof(double) * (g.sq_max + 1), hipMemcpyDeviceToHost), "hipMemcpy");
-  if (!rc && memcmp(back, sq, sizeof(double) * (g.sq_max + 1)) != 0)
+  if (!rc) rc = check_hip(hipMalloc(&probe, sizeof(double) * nsq), "hipMalloc");
+  if (!rc)
+    rc = launch_kernel(sqrt_probe_kernel, dim3((unsigned)(g.sq_max / 256 + 1)), dim3(256), 0, nullptr, nullptr,
+                       nullptr, "sqrt_probe_kernel launch", QUIET, probe, g.sq_max);
+  if (!rc) rc = check_hip(hipMemcpy(back.get(), probe, sizeof(double) * nsq, hipMemcpyDeviceToHost), "hipMemcpy");
+  if (!rc && memcmp(back.get(), sq.get(), sizeof(double) * nsq) != 0)
     rc = perr(MAPFX_EINVAL, "MARL_PARTIAL: the device fp64 sqrt differs from host libm (observations would not match)");
   if (probe) (void)hipFree(probe);
-  free(back);
-  free(sq);
-  free(bo);
-  if (rc) {
-    mapfx_partial_destroy(h);
-    return rc;
-  }
-  *out = h;
+  if (rc) return rc;
+  *out = h.release();
   return MAPFX_OK;
 }
 
@@ -2185,50 +2138,20 @@ int mapfx_partial_goal_dist(mapfx_partial_t* h, const mapfx_partial_state* st,
   const PGeo& g = h->geo;
   if ((long long)g.E * g.N == 0) return MAPFX_OK;
   const hipStream_t sm = (hipStream_t)stream;
-  const dim3 grid((unsigned)(g.E * g.N));
-  const void* bfs = nullptr;  // the BFS instance launched (mapfx_last_kernel)
-  if (g.huge_lds) {
-    if (g.gd32) {
-      bfs = (const void*)partial_bfs_huge_kernel<int32_t>;
-      hipLaunchKernelGGL(partial_bfs_huge_kernel<int32_t>, grid, dim3(HUGE_THREADS), g.huge_lds, sm, g,
-                         st->map_bits, st->goal, env_mask, (int32_t*)st->goal_dist);
-    } else {
-      bfs = (const void*)partial_bfs_huge_kernel<int16_t>;
-      hipLaunchKernelGGL(partial_bfs_huge_kernel<int16_t>, grid, dim3(HUGE_THREADS), g.huge_lds, sm, g,
-                         st->map_bits, st->goal, env_mask, (int16_t*)st->goal_dist);
-    }
-  } else if (g.H <= 64 && g.W <= 64) {
-    if (g.gd8) {
-      bfs = (const void*)partial_bfs_kernel<uint8_t>;
-      hipLaunchKernelGGL(partial_bfs_kernel<uint8_t>, grid, dim3(64), 0, sm, g, st->map_bits, st->goal,
-                         env_mask, (uint8_t*)st->goal_dist);
-    } else {
-      bfs = (const void*)partial_bfs_kernel<int16_t>;
-      hipLaunchKernelGGL(partial_bfs_kernel<int16_t>, grid, dim3(64), 0, sm, g, st->map_bits, st->goal,
-                         env_mask, (int16_t*)st->goal_dist);
-    }
-  } else {
-    if (g.gd32) {
-      bfs = (const void*)partial_bfs_big_kernel<int32_t>;
-      hipLaunchKernelGGL(partial_bfs_big_kernel<int32_t>, grid, dim3(256), 0, sm, g, st->map_bits,
-                         st->goal, env_mask, (int32_t*)st->goal_dist);
-    } else if (g.gd8) {
-      bfs = (const void*)partial_bfs_big_kernel<uint8_t>;
-      hipLaunchKernelGGL(partial_bfs_big_kernel<uint8_t>, grid, dim3(256), 0, sm, g, st->map_bits,
-                         st->goal, env_mask, (uint8_t*)st->goal_dist);
-    } else {
-      bfs = (const void*)partial_bfs_big_kernel<int16_t>;
-      hipLaunchKernelGGL(partial_bfs_big_kernel<int16_t>, grid, dim3(256), 0, sm, g, st->map_bits,
-                         st->goal, env_mask, (int16_t*)st->goal_dist);
-    }
-  }
-  mapfx_note_kernel(bfs);  // (not pdist_invalidate_kernel below)
-  rc = check_hip(hipGetLastError(), "partial_bfs_kernel launch");
+  if (g.huge_lds)
+    rc = g.gd32 ? launch_bfs(partial_bfs_huge_kernel<int32_t>, HUGE_THREADS, g.huge_lds, g, st, env_mask, sm)
+                : launch_bfs(partial_bfs_huge_kernel<int16_t>, HUGE_THREADS, g.huge_lds, g, st, env_mask, sm);
+  else if (g.H <= 64 && g.W <= 64)
+    rc = g.gd8 ? launch_bfs(partial_bfs_kernel<uint8_t>, 64, 0, g, st, env_mask, sm)
+               : launch_bfs(partial_bfs_kernel<int16_t>, 64, 0, g, st, env_mask, sm);
+  else
+    rc = g.gd32  ? launch_bfs(partial_bfs_big_kernel<int32_t>, 256, 0, g, st, env_mask, sm)
+         : g.gd8 ? launch_bfs(partial_bfs_big_kernel<uint8_t>, 256, 0, g, st, env_mask, sm)
+                 : launch_bfs(partial_bfs_big_kernel<int16_t>, 256, 0, g, st, env_mask, sm);
   if (rc || !st->pdist) return rc;
-  const long long total = (long long)g.E * g.N;
-  hipLaunchKernelGGL(pdist_invalidate_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, sm, total,
-                     g.N, env_mask, st->pdist);
-  return check_hip(hipGetLastError(), "pdist_invalidate_kernel launch");
+  const long long total = (long long)g.E * g.N;  // (QUIET: the recorded kernel stays the BFS instance)
+  return launch_kernel(pdist_invalidate_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, sm, nullptr,
+                       nullptr, "pdist_invalidate_kernel launch", QUIET, total, g.N, env_mask, st->pdist);
 }
 
 int mapfx_partial_draw(mapfx_partial_t* h, const mapfx_partial_scen* sc, void* stream) {
@@ -2258,14 +2181,9 @@ int mapfx_partial_draw(mapfx_partial_t* h, const mapfx_partial_scen* sc, void* s
   unsigned P = 2;
   while (P < (unsigned)sc->l_max) P <<= 1;
   const hipStream_t sm = (hipStream_t)stream;
-  if (sc->l_max <= SCEN_WAVE_LMAX) {
-    hipLaunchKernelGGL(partial_draw_kernel<64>, dim3((unsigned)g.E), dim3(64), P * 8u, sm, a);
-    mapfx_note_kernel((const void*)partial_draw_kernel<64>);
-  } else {
-    hipLaunchKernelGGL(partial_draw_kernel<256>, dim3((unsigned)g.E), dim3(256), P * 8u, sm, a);
-    mapfx_note_kernel((const void*)partial_draw_kernel<256>);
-  }
-  return check_hip(hipGetLastError(), "partial_draw_kernel launch");
+  const bool wave = sc->l_max <= SCEN_WAVE_LMAX;
+  return launch_kernel(wave ? partial_draw_kernel<64> : partial_draw_kernel<256>, dim3((unsigned)g.E),
+                       dim3(wave ? 64 : 256), P * 8u, sm, nullptr, nullptr, "partial_draw_kernel launch", NOTED, a);
 }
 
 int mapfx_partial_reset(mapfx_partial_t* h, const mapfx_partial_state* st, const uint8_t* env_mask,

@@ -32,6 +32,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <new>
 
 #include "internal.h"
@@ -74,12 +75,6 @@ struct QArgs {
   const double* pow_lut;  // (double)n ** .5 by host libm pow, n = 0 .. lut_n-1
 };
 
-__device__ inline void wave_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // dirDict (:28) as 2-bit fields of (d + 1), action a at bits 2a:
 // a:      0  1  2  3  4  5  6  7  8
 // row+1:  1  1  2  1  0  2  2  0  0      col+1:  1  2  1  0  1  2  0  0  2
@@ -92,9 +87,6 @@ __device__ inline int opposite(int a) { return a == 0 ? -1 : (a <= 4 ? ((a + 1) 
 // the action whose direction is (dr, dc), |dr|, |dc| <= 1 (index (dr + 1) * 3 + dc + 1), 0 for (0, 0)
 constexpr uint64_t ACT_OF = 7ull | 4ull << 4 | 8ull << 8 | 3ull << 12 | 0ull << 16 | 1ull << 20 |
                             6ull << 24 | 2ull << 28 | 5ull << 32;
-
-// x / d for 0 <= x < 2^32 with m = ceil(2^48 / d)
-__device__ inline int fdiv(int x, uint64_t m) { return (int)(((uint64_t)(uint32_t)x * m) >> 48); }
 
 // S: observation size fixed at compile time (0: g.s); LS: log2(lanes per world);
 // DIAG: DIAGONAL_MOVEMENT; MA: agents per lane held in registers (>= g.apl).
@@ -316,8 +308,8 @@ __global__ void __launch_bounds__(64) primal_act_kernel(QGeo g, QArgs a) {
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
               const int b = 4 * m + t;
-              const int pl = fdiv(b, g.m_ss), i = b - pl * ss;
-              const int y = fdiv(i, g.m_s), x = i - y * s;
+              const int pl = fastdiv(b, g.m_ss), i = b - pl * ss;
+              const int y = fastdiv(i, g.m_s), x = i - y * s;
               const uint32_t v = cm[base + y * PW + x];
               uint32_t bv;
               if (pl == 0) bv = v & 1u;
@@ -705,17 +697,6 @@ __global__ void __launch_bounds__(64) primal_seq_kernel(QGeo g, QArgs a) {
   }
 }
 
-int perr(int code, const char* msg) { return mapfx_internal_error(code, msg); }
-
-int check_hip(hipError_t err, const char* what) {
-  if (err != hipSuccess) {
-    char buf[256];
-    snprintf(buf, sizeof(buf), "%s: %s", what, hipGetErrorString(err));
-    return perr(MAPFX_EHIP, buf);
-  }
-  return MAPFX_OK;
-}
-
 }  // namespace
 
 struct mapfx_primal_t {
@@ -749,9 +730,6 @@ PrimalFn pick_primal(const QGeo& g) {
   return g.diag ? pick_ls<0, true>(g.lw_shift, g.apl) : pick_ls<0, false>(g.lw_shift, g.apl);
 }
 
-uint64_t magic48(int d) { return ((1ull << 48) + (uint64_t)d - 1) / (uint64_t)d; }
-int r16(int x) { return (x + 15) & ~15; }
-
 template <bool DIAG>
 PrimalFn pick_seq_s(int s) {
   if (s == 4) return primal_seq_kernel<4, DIAG>;
@@ -768,13 +746,13 @@ int layout_seq(QGeo& g) {
   const bool ok = g.s % 2 == 0 && g.s >= 4 && g.s <= 10 && g.N <= 64 && g.H + 2 * g.P <= 64 &&
                   g.W + 2 * g.P <= 64;
   if (!ok) return 0;
-  int o = r16((g.H + 2 * g.P) * 8);
+  int o = round_up((g.H + 2 * g.P) * 8, 16);
   g.off_gl = o;
-  o += r16(4 * g.N);
+  o += round_up(4 * g.N, 16);
   g.off_snap = o;
-  o += r16(65 * 2 * g.N + 2);  // 65 rows + the spare slot of the non-agent lanes
+  o += round_up(65 * 2 * g.N + 2, 16);  // 65 rows + the spare slot of the non-agent lanes
   g.off_psnap = o;
-  if (g.diag) o += r16(65 * 2 * g.N + 2);
+  if (g.diag) o += round_up(65 * 2 * g.N + 2, 16);
   g.off_bstr = o;
   o += 64 * 64;
   return o;
@@ -782,11 +760,11 @@ int layout_seq(QGeo& g) {
 
 // LDS layout of one world for lanes-per-world 1 << ls; returns its size.
 int layout(QGeo& g) {
-  int o = r16(g.rows * g.PW + 4);  // + the realigning read's overrun
+  int o = round_up(g.rows * g.PW + 4, 16);  // + the realigning read's overrun
   g.off_bm = o;
-  o += r16(g.bits_words * 4);
+  o += round_up(g.bits_words * 4, 16);
   g.off_goals = o;
-  o += r16(g.s * g.s + 4);
+  o += round_up(g.s * g.s + 4, 16);
   g.off_ag = o;
   o += 16 * g.N;
   g.off_pair = o;
@@ -797,7 +775,7 @@ int layout(QGeo& g) {
   o += 64 * 8;
   g.off_fst = o;
   o += 5 * 64;
-  return r16(o);
+  return round_up(o, 16);
 }
 
 // ---------------------------------------------------------------------------
@@ -1115,9 +1093,8 @@ int launch_blocking(mapfx_primal_t* h, const BArgs& a, void* stream) {
   const bool rows = g.H <= 64 && g.W <= 64 && !h->blocking_flat;
   const int lds = (rows ? 64 * 8 : (g.hw + 63) / 64 * 8 * 5) + g.N * 16;  // + positions, goals
   const PrimalBFn fn = rows ? primal_blocking_kernel<true> : primal_blocking_kernel<false>;
-  hipLaunchKernelGGL(fn, dim3((unsigned)(g.E * a.K)), dim3(64), lds, (hipStream_t)stream, g, a);
-  mapfx_note_kernel((const void*)fn);
-  return check_hip(hipGetLastError(), "primal_blocking_kernel launch");
+  return launch_kernel(fn, dim3((unsigned)(g.E * a.K)), dim3(64), lds, (hipStream_t)stream, nullptr, nullptr,
+                       "primal_blocking_kernel launch", NOTED, g, a);
 }
 
 // ---------------------------------------------------------------------------
@@ -1201,7 +1178,7 @@ __global__ void __launch_bounds__(1024) primal_observe_kernel(QGeo g, OArgs a) {
   // ---- cells over lanes: obstacle and own-goal planes, poss_map / goals_map cleared ----
   if (a.obs) {
     for (int i = lane; i < ss; i += 64) {
-      const int y = S_ ? i / s : fdiv(i, g.m_s), x = i - y * s;
+      const int y = S_ ? i / s : fastdiv(i, g.m_s), x = i - y * s;
       const int r = tr + y, c = tc + x;
       const bool in = r >= 0 && r < H && c >= 0 && c < W;
       const int idx = in ? r * W + c : 0;
@@ -1481,7 +1458,7 @@ __global__ void __launch_bounds__(64) primal_observe_packed_kernel(QGeo g, OArgs
   }
   uint32_t* o32 = (uint32_t*)(a.obs + f0 * 4 * ss);
   for (int d = d0 + lane; d < nd; d += 64) {
-    const int owner = fdiv(d, g.m_ss);
+    const int owner = fastdiv(d, g.m_ss);
     if ((okm >> owner) & 1ull) o32[d] = nibble_bytes(str[d >> 3] >> (4 * (d & 7)));
   }
 }
@@ -1535,14 +1512,8 @@ constexpr uint64_t GK_ENV = 0xD1B54A32D192ED03ull, GK_T = 0xABC98388FB8FAC03ull,
                    GK_CELL = 0x9E6C63D0676A9A99ull, GK_STREAM = 0xF1357AEA2E62A9C5ull;
 constexpr uint32_t GS_WORLD = 0x100u, GS_OBST = 0x200u, GS_START = 0x300u, GS_GOAL = 0x400u;
 
-__device__ inline uint64_t gen_mix(uint64_t x) {  // splitmix64 (mapfx.hip)
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
 __device__ inline uint64_t gen_key(uint64_t base, uint32_t stream, uint32_t idx) {
-  return gen_mix(base ^ ((uint64_t)idx * GK_CELL) ^ ((uint64_t)stream * GK_STREAM));
+  return splitmix64(base ^ ((uint64_t)idx * GK_CELL) ^ ((uint64_t)stream * GK_STREAM));
 }
 __device__ inline uint32_t gen_draw32(uint64_t base, uint32_t stream, uint32_t idx) {
   return (uint32_t)(gen_key(base, stream, idx) >> 32);
@@ -1723,6 +1694,22 @@ __global__ void __launch_bounds__(64 * GEN_WAVES) primal_generate_kernel(QGeo g,
   if (lane == 0) a.episode[e] = ep + 1;
 }
 
+// the checks every entry point that reads the worlds starts with
+int check_state(const mapfx_primal_t* h, const mapfx_primal_state* st) {
+  if (!h) return perr(MAPFX_EINVAL, "NULL handle");
+  if (!st || !st->pos || !st->goal || !st->map_bits) return perr(MAPFX_EINVAL, "bad state");
+  return MAPFX_OK;
+}
+
+// a zeroed QArgs / OArgs / BArgs with the worlds' pos / goal / bits
+template <typename A>
+void fill_state(A& a, const mapfx_primal_state* st) {
+  memset(&a, 0, sizeof(a));
+  a.pos = st->pos;
+  a.goal = st->goal;
+  a.bits = st->map_bits;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1736,7 +1723,8 @@ int mapfx_primal_create(const mapfx_primal_cfg* cfg, mapfx_primal_t** out) {
   if (c.n_agents < 1 || c.n_agents > 255) return perr(MAPFX_EINVAL, "n_agents must be in 1..255");
   if (c.n_envs < 0) return perr(MAPFX_EINVAL, "n_envs < 0");
   if (c.obs_size < 1 || c.obs_size > 32) return perr(MAPFX_EINVAL, "obs_size must be in 1..32");
-  mapfx_primal_t* h = new (std::nothrow) mapfx_primal_t();
+  std::unique_ptr<mapfx_primal_t, void (*)(mapfx_primal_t*)> h(new (std::nothrow) mapfx_primal_t(),
+                                                               mapfx_primal_destroy);
   if (!h) return perr(MAPFX_ENOMEM, "host allocation failed");
   QGeo& g = h->geo;
   memset(&g, 0, sizeof(g));
@@ -1782,10 +1770,7 @@ int mapfx_primal_create(const mapfx_primal_cfg* cfg, mapfx_primal_t** out) {
   else
     while (ls < 6 && (long long)(g.E + (64 >> ls) - 1) / (64 >> ls) < 2048) ++ls;
   while (ls < 6 && (64 >> ls) * wreg > 65536) ++ls;
-  if ((64 >> ls) * wreg > 160 * 1024) {
-    delete h;
-    return perr(MAPFX_EINVAL, "PRIMAL world needs too much LDS");
-  }
+  if ((64 >> ls) * wreg > 160 * 1024) return perr(MAPFX_EINVAL, "PRIMAL world needs too much LDS");
   g.lw_shift = ls;
   g.lw = 1 << ls;
   g.apl = (g.N + g.lw - 1) / g.lw;
@@ -1800,27 +1785,17 @@ int mapfx_primal_create(const mapfx_primal_cfg* cfg, mapfx_primal_t** out) {
   if (h->lds > 64 * 1024) {
     const hipError_t e = hipFuncSetAttribute((const void*)pick_primal(g),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, h->lds);
-    if (e != hipSuccess) {
-      delete h;
-      return check_hip(e, "hipFuncSetAttribute");
-    }
+    if (e != hipSuccess) return check_hip(e, "hipFuncSetAttribute");
   }
   double* lut = (double*)malloc(sizeof(double) * g.lut_n);
-  if (!lut) {
-    delete h;
-    return perr(MAPFX_ENOMEM, "host allocation failed");
-  }
+  if (!lut) return perr(MAPFX_ENOMEM, "host allocation failed");
   double (*volatile libm_pow)(double, double) = pow;  // `n ** .5` in Python = libm pow
   for (int i = 0; i < g.lut_n; ++i) lut[i] = libm_pow((double)i, 0.5);
-  h->pow_lut = nullptr;
   int rc = check_hip(hipMalloc(&h->pow_lut, sizeof(double) * g.lut_n), "hipMalloc");
   if (!rc) rc = check_hip(hipMemcpy(h->pow_lut, lut, sizeof(double) * g.lut_n, hipMemcpyHostToDevice), "hipMemcpy");
   free(lut);
-  if (rc) {
-    mapfx_primal_destroy(h);
-    return rc;
-  }
-  *out = h;
+  if (rc) return rc;
+  *out = h.release();
   return MAPFX_OK;
 }
 
@@ -1833,8 +1808,7 @@ void mapfx_primal_destroy(mapfx_primal_t* h) {
 int mapfx_primal_act_timed(mapfx_primal_t* h, const mapfx_primal_state* st, const int32_t* agent_ids,
                            const int32_t* actions, int32_t K, const mapfx_primal_out* out,
                            void* start_event, void* stop_event, void* stream) {
-  if (!h) return perr(MAPFX_EINVAL, "NULL handle");
-  if (!st || !st->pos || !st->goal || !st->map_bits) return perr(MAPFX_EINVAL, "bad state");
+  if (const int rc = check_state(h, st)) return rc;
   if (h->geo.diag && !st->past) return perr(MAPFX_EINVAL, "diagonal movement needs state.past");
   if (K < 0) return perr(MAPFX_EINVAL, "K < 0");
   // (both kernels write the observation records as dwords)
@@ -1842,10 +1816,7 @@ int mapfx_primal_act_timed(mapfx_primal_t* h, const mapfx_primal_state* st, cons
   if (K == 0 || h->geo.E == 0) return MAPFX_OK;
   if (!agent_ids || !actions) return perr(MAPFX_EINVAL, "NULL agent_ids / actions");
   QArgs a;
-  memset(&a, 0, sizeof(a));
-  a.pos = st->pos;
-  a.goal = st->goal;
-  a.bits = st->map_bits;
+  fill_state(a, st);
   a.past = st->past;
   a.ids = agent_ids;
   a.acts = actions;
@@ -1862,23 +1833,12 @@ int mapfx_primal_act_timed(mapfx_primal_t* h, const mapfx_primal_state* st, cons
     a.err = out->err;
   }
   const QGeo& g = h->geo;
-  if (g.seq && ((uintptr_t)a.obs & 15u) == 0) {  // (16-byte record runs)
-    if (start_event || stop_event)
-      hipExtLaunchKernelGGL(pick_seq(g), dim3(g.E), dim3(64), g.lds_seq, (hipStream_t)stream,
-                            (hipEvent_t)start_event, (hipEvent_t)stop_event, 0, g, a);
-    else
-      hipLaunchKernelGGL(pick_seq(g), dim3(g.E), dim3(64), g.lds_seq, (hipStream_t)stream, g, a);
-    mapfx_note_kernel((const void*)pick_seq(g));
-    return check_hip(hipGetLastError(), "primal_seq_kernel launch");
-  }
+  if (g.seq && ((uintptr_t)a.obs & 15u) == 0)  // (16-byte record runs)
+    return launch_kernel(pick_seq(g), dim3(g.E), dim3(64), g.lds_seq, (hipStream_t)stream, (hipEvent_t)start_event,
+                         (hipEvent_t)stop_event, "primal_seq_kernel launch", NOTED, g, a);
   const int wpw = 64 >> g.lw_shift;
-  if (start_event || stop_event)
-    hipExtLaunchKernelGGL(pick_primal(g), dim3((g.E + wpw - 1) / wpw), dim3(64), h->lds, (hipStream_t)stream,
-                          (hipEvent_t)start_event, (hipEvent_t)stop_event, 0, g, a);
-  else
-    hipLaunchKernelGGL(pick_primal(g), dim3((g.E + wpw - 1) / wpw), dim3(64), h->lds, (hipStream_t)stream, g, a);
-  mapfx_note_kernel((const void*)pick_primal(g));
-  return check_hip(hipGetLastError(), "primal_act_kernel launch");
+  return launch_kernel(pick_primal(g), dim3((g.E + wpw - 1) / wpw), dim3(64), h->lds, (hipStream_t)stream,
+                       (hipEvent_t)start_event, (hipEvent_t)stop_event, "primal_act_kernel launch", NOTED, g, a);
 }
 
 int mapfx_primal_act(mapfx_primal_t* h, const mapfx_primal_state* st, const int32_t* agent_ids,
@@ -1888,8 +1848,7 @@ int mapfx_primal_act(mapfx_primal_t* h, const mapfx_primal_state* st, const int3
 
 int mapfx_primal_observe(mapfx_primal_t* h, const mapfx_primal_state* st, const int32_t* agent_ids,
                          const int32_t* prev_actions, int32_t Q, const mapfx_primal_out* out, void* stream) {
-  if (!h) return perr(MAPFX_EINVAL, "NULL handle");
-  if (!st || !st->pos || !st->goal || !st->map_bits) return perr(MAPFX_EINVAL, "bad state");
+  if (const int rc = check_state(h, st)) return rc;
   const QGeo& g = h->geo;
   if (g.diag && !st->past) return perr(MAPFX_EINVAL, "diagonal movement needs state.past");
   if (Q < 0) return perr(MAPFX_EINVAL, "Q < 0");
@@ -1897,10 +1856,7 @@ int mapfx_primal_observe(mapfx_primal_t* h, const mapfx_primal_state* st, const 
   if (out && ((uintptr_t)out->obs & 3u)) return perr(MAPFX_EINVAL, "out->obs must be 4-byte aligned");
   if (Q == 0 || g.E == 0) return MAPFX_OK;
   OArgs a;
-  memset(&a, 0, sizeof(a));
-  a.pos = st->pos;
-  a.goal = st->goal;
-  a.bits = st->map_bits;
+  fill_state(a, st);
   a.past = st->past;
   a.ids = agent_ids;
   a.prev = prev_actions;
@@ -1922,10 +1878,10 @@ int mapfx_primal_observe(mapfx_primal_t* h, const mapfx_primal_state* st, const 
   // the records leave as 16-byte stores; else one wave per query.  MAPFX_PRIMAL_OBSERVE
   // = waves / lanes pins either (tests; lanes still needs the LDS to fit).
   {
-    const int strs = r16((8 * g.s * g.s + 1) * 4);
-    a.w_ag = r16(g.bits_words * 4);
+    const int strs = round_up((8 * g.s * g.s + 1) * 4, 16);
+    a.w_ag = round_up(g.bits_words * 4, 16);
     a.w_past = a.w_ag + 16 * g.N;
-    const int per_world = a.w_past + (g.diag ? r16(8 * g.N) : 0);
+    const int per_world = a.w_past + (g.diag ? round_up(8 * g.N, 16) : 0);
     const long long total = (long long)g.E * Q;
     const int wmax = (int)std::min<long long>(g.E, 63 / Q + 2);
     const long long lds = strs + (long long)wmax * per_world;
@@ -1937,40 +1893,34 @@ int mapfx_primal_observe(mapfx_primal_t* h, const mapfx_primal_state* st, const 
       a.off_ag = strs;
       a.rec_bytes = per_world;
       const PrimalOFn fn = g.diag ? primal_observe_packed_kernel<true> : primal_observe_packed_kernel<false>;
-      hipLaunchKernelGGL(fn, dim3((unsigned)((total + 63) / 64)), dim3(64), (int)lds, (hipStream_t)stream, g, a);
-      mapfx_note_kernel((const void*)fn);
-      return check_hip(hipGetLastError(), "primal_observe_packed_kernel launch");
+      return launch_kernel(fn, dim3((unsigned)((total + 63) / 64)), dim3(64), (int)lds, (hipStream_t)stream, nullptr,
+                           nullptr, "primal_observe_packed_kernel launch", NOTED, g, a);
     }
   }
   // LDS of a workgroup: bitmap (<= 2 KB), agent records (<= 4 KB, DIAG + 2 KB), one
   // 4 s^2-byte slab per wave (<= 4 KB): with up to 16 waves at most 72 KB, so the waves
   // are capped to stay inside the 64 KB every kernel gets without an attribute.
-  a.off_ag = r16(g.bits_words * 4);
+  a.off_ag = round_up(g.bits_words * 4, 16);
   a.off_past = a.off_ag + 16 * g.N;
-  a.off_rec = a.off_past + (g.diag ? r16(8 * g.N) : 0);
-  a.rec_bytes = r16(4 * g.s * g.s);
+  a.off_rec = a.off_past + (g.diag ? round_up(8 * g.N, 16) : 0);
+  a.rec_bytes = round_up(4 * g.s * g.s, 16);
   const int maxw = std::min(16, (64 * 1024 - a.off_rec) / a.rec_bytes);
   a.chunks = (Q + maxw - 1) / maxw;
   a.nw = (Q + a.chunks - 1) / a.chunks;  // the world's queries spread evenly over its workgroups
   if ((long long)g.E * a.chunks > 0x7FFFFFFFll) return perr(MAPFX_EINVAL, "n_envs * Q too large");
   const int lds = a.off_rec + a.nw * a.rec_bytes;
   const PrimalOFn fn = pick_observe(g);
-  hipLaunchKernelGGL(fn, dim3((unsigned)(g.E * a.chunks)), dim3(64 * a.nw), lds, (hipStream_t)stream, g, a);
-  mapfx_note_kernel((const void*)fn);
-  return check_hip(hipGetLastError(), "primal_observe_kernel launch");
+  return launch_kernel(fn, dim3((unsigned)(g.E * a.chunks)), dim3(64 * a.nw), lds, (hipStream_t)stream, nullptr,
+                       nullptr, "primal_observe_kernel launch", NOTED, g, a);
 }
 
 int mapfx_primal_blocking_count(mapfx_primal_t* h, const mapfx_primal_state* st, const int32_t* agent_ids,
                                 int32_t* counts, void* stream) {
-  if (!h) return perr(MAPFX_EINVAL, "NULL handle");
-  if (!st || !st->pos || !st->goal || !st->map_bits) return perr(MAPFX_EINVAL, "bad state");
+  if (const int rc = check_state(h, st)) return rc;
   if (!agent_ids || !counts) return perr(MAPFX_EINVAL, "NULL agent_ids / counts");
   if (h->geo.E == 0) return MAPFX_OK;
   BArgs a;
-  memset(&a, 0, sizeof(a));
-  a.pos = st->pos;
-  a.goal = st->goal;
-  a.bits = st->map_bits;
+  fill_state(a, st);
   a.ids = agent_ids;
   a.K = 1;
   a.counts = counts;
@@ -1980,17 +1930,13 @@ int mapfx_primal_blocking_count(mapfx_primal_t* h, const mapfx_primal_state* st,
 int mapfx_primal_blocking(mapfx_primal_t* h, const mapfx_primal_state* st, const int32_t* agent_ids,
                           const int32_t* actions, int32_t K, const uint8_t* valid, const uint8_t* on_goal,
                           double* reward, uint8_t* blocking, int32_t* counts, void* stream) {
-  if (!h) return perr(MAPFX_EINVAL, "NULL handle");
-  if (!st || !st->pos || !st->goal || !st->map_bits) return perr(MAPFX_EINVAL, "bad state");
+  if (const int rc = check_state(h, st)) return rc;
   if (K < 0) return perr(MAPFX_EINVAL, "K < 0");
   if (!valid || !on_goal) return perr(MAPFX_EINVAL, "the blocking pass needs the launch's valid and on_goal");
   if (K == 0 || h->geo.E == 0) return MAPFX_OK;
   if (!agent_ids || !actions) return perr(MAPFX_EINVAL, "NULL agent_ids / actions");
   BArgs a;
-  memset(&a, 0, sizeof(a));
-  a.pos = st->pos;
-  a.goal = st->goal;
-  a.bits = st->map_bits;
+  fill_state(a, st);
   a.ids = agent_ids;
   a.acts = actions;
   a.K = K;
@@ -2036,10 +1982,9 @@ int mapfx_primal_generate(mapfx_primal_t* h, const mapfx_primal_state* st, const
   a.pos = st->pos;
   a.goal = const_cast<int32_t*>(st->goal);
   a.past = g.diag ? st->past : nullptr;
-  hipLaunchKernelGGL(primal_generate_kernel, dim3((unsigned)((g.E + GEN_WAVES - 1) / GEN_WAVES)),
-                     dim3(64 * GEN_WAVES), 0, (hipStream_t)stream, g, a);
-  mapfx_note_kernel((const void*)primal_generate_kernel);
-  return check_hip(hipGetLastError(), "primal_generate_kernel launch");
+  return launch_kernel(primal_generate_kernel, dim3((unsigned)((g.E + GEN_WAVES - 1) / GEN_WAVES)),
+                       dim3(64 * GEN_WAVES), 0, (hipStream_t)stream, nullptr, nullptr,
+                       "primal_generate_kernel launch", NOTED, g, a);
 }
 
 }  // extern "C"

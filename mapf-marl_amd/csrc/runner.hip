@@ -24,13 +24,6 @@ namespace {
 
 constexpr int RB = 256;  // threads of a row-copy workgroup
 
-int err(int code, const char* msg) { return mapfx_internal_error(code, msg); }
-
-int launch_ok(const char* what) {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? MAPFX_OK : err(MAPFX_EHIP, what);
-}
-
 // obs / state / avail_actions (+ filled = 1) of env b into time row t
 __device__ inline void write_pre(const mapfx_runner_state& rs, const mapfx_partial_out& o,
                                  const mapfx_episode_rows& r, int b, int t) {
@@ -194,7 +187,7 @@ __global__ void __launch_bounds__(CT) runner_compact_kernel(mapfx_runner_state r
 int check_rs(const mapfx_runner_state* rs) {
   if (!rs || rs->B < 0 || rs->N < 1 || rs->D < 0 || !rs->alive || !rs->alive_prev || !rs->bs ||
       !rs->counts || !rs->ep_return || !rs->ep_length || !rs->env_steps || !rs->env_actions)
-    return err(MAPFX_EINVAL, "runner state: NULL field or bad B/N/D");
+    return perr(MAPFX_EINVAL, "runner state: NULL field or bad B/N/D");
   return MAPFX_OK;
 }
 
@@ -207,10 +200,10 @@ int mapfx_runner_begin(const mapfx_runner_state* rs, const mapfx_partial_out* ou
   int rc = check_rs(rs);
   if (rc) return rc;
   if (!out || !rows || !out->obs || !out->state || !out->avail)
-    return err(MAPFX_EINVAL, "runner_begin: NULL out / rows");
+    return perr(MAPFX_EINVAL, "runner_begin: NULL out / rows");
   if (rs->B == 0) return MAPFX_OK;
-  hipLaunchKernelGGL(runner_begin_kernel, dim3(rs->B), dim3(RB), 0, (hipStream_t)stream, *rs, *out, *rows);
-  return launch_ok("runner_begin_kernel launch");
+  return launch_kernel(runner_begin_kernel, dim3(rs->B), dim3(RB), 0, (hipStream_t)stream, nullptr, nullptr,
+                       "runner_begin_kernel launch", QUIET, *rs, *out, *rows);
 }
 
 int mapfx_runner_actions(const mapfx_runner_state* rs, const void* actions, int32_t action_dtype,
@@ -218,14 +211,14 @@ int mapfx_runner_actions(const mapfx_runner_state* rs, const void* actions, int3
                          void* stream) {
   int rc = check_rs(rs);
   if (rc) return rc;
-  if (!actions || !rows) return err(MAPFX_EINVAL, "runner_actions: NULL actions / rows");
-  if (action_dtype < MAPFX_I8 || action_dtype > MAPFX_I64) return err(MAPFX_EINVAL, "runner_actions: bad dtype");
-  if (ts < 0 || ts >= rows->max_t) return err(MAPFX_EINVAL, "runner_actions: ts outside the batch");
+  if (!actions || !rows) return perr(MAPFX_EINVAL, "runner_actions: NULL actions / rows");
+  if (action_dtype < MAPFX_I8 || action_dtype > MAPFX_I64) return perr(MAPFX_EINVAL, "runner_actions: bad dtype");
+  if (ts < 0 || ts >= rows->max_t) return perr(MAPFX_EINVAL, "runner_actions: ts outside the batch");
   const int64_t total = (int64_t)rs->B * rs->N;
   if (total == 0) return MAPFX_OK;
-  hipLaunchKernelGGL(runner_actions_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
-                     (hipStream_t)stream, *rs, actions, (int)action_dtype, row_stride, (int)ts, *rows);
-  return launch_ok("runner_actions_kernel launch");
+  return launch_kernel(runner_actions_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, nullptr, nullptr, "runner_actions_kernel launch", QUIET, *rs, actions,
+                       (int)action_dtype, row_stride, (int)ts, *rows);
 }
 
 int mapfx_runner_post(const mapfx_runner_state* rs, const uint8_t* terminated,
@@ -234,14 +227,14 @@ int mapfx_runner_post(const mapfx_runner_state* rs, const uint8_t* terminated,
   int rc = check_rs(rs);
   if (rc) return rc;
   if (!terminated || !out || !rows || !out->reward || !out->obs || !out->state || !out->avail)
-    return err(MAPFX_EINVAL, "runner_post: NULL terminated / out / rows");
-  if (ts < 0 || ts >= rows->max_t) return err(MAPFX_EINVAL, "runner_post: ts outside the batch");
+    return perr(MAPFX_EINVAL, "runner_post: NULL terminated / out / rows");
+  if (ts < 0 || ts >= rows->max_t) return perr(MAPFX_EINVAL, "runner_post: ts outside the batch");
   if (rs->B == 0) return MAPFX_OK;
-  hipLaunchKernelGGL(runner_post_kernel, dim3(rs->B), dim3(RB), 0, (hipStream_t)stream, *rs, terminated,
-                     *out, (int)ts, *rows);
-  if ((rc = launch_ok("runner_post_kernel launch"))) return rc;
-  hipLaunchKernelGGL(runner_compact_kernel, dim3(1), dim3(CT), 0, (hipStream_t)stream, *rs, counts_out);
-  return launch_ok("runner_compact_kernel launch");
+  rc = launch_kernel(runner_post_kernel, dim3(rs->B), dim3(RB), 0, (hipStream_t)stream, nullptr, nullptr,
+                     "runner_post_kernel launch", QUIET, *rs, terminated, *out, (int)ts, *rows);
+  if (rc) return rc;
+  return launch_kernel(runner_compact_kernel, dim3(1), dim3(CT), 0, (hipStream_t)stream, nullptr, nullptr,
+                       "runner_compact_kernel launch", QUIET, *rs, counts_out);
 }
 
 int mapfx_runner_step(mapfx_partial_t* h, const mapfx_partial_state* st, const mapfx_partial_out* out,
@@ -250,8 +243,8 @@ int mapfx_runner_step(mapfx_partial_t* h, const mapfx_partial_state* st, const m
                       const mapfx_episode_rows* rows, void* stream) {
   int rc = check_rs(rs);
   if (rc) return rc;
-  if (!rows) return err(MAPFX_EINVAL, "runner_step: NULL rows");
-  if (ts < 0 || ts >= rows->max_t) return err(MAPFX_EINVAL, "runner_step: ts outside the batch");
+  if (!rows) return perr(MAPFX_EINVAL, "runner_step: NULL rows");
+  if (ts < 0 || ts >= rows->max_t) return perr(MAPFX_EINVAL, "runner_step: ts outside the batch");
   if (!rs->bs_inv)  // the unfused form: a separate actions pass into env_actions
     return (rc = mapfx_runner_actions(rs, actions, action_dtype, row_stride, ts, rows, stream)) ? rc
            : (rc = mapfx_partial_step(h, st, rs->env_actions, MAPFX_I8, out, stream))
@@ -318,16 +311,16 @@ int mapfx_runner_step(mapfx_partial_t* h, const mapfx_partial_state* st, const m
 }
 
 int mapfx_host_ring_alloc(int32_t n, int32_t** host_ptr, int32_t** dev_ptr) {
-  if (n < 1 || !host_ptr || !dev_ptr) return err(MAPFX_EINVAL, "host_ring_alloc: bad arguments");
+  if (n < 1 || !host_ptr || !dev_ptr) return perr(MAPFX_EINVAL, "host_ring_alloc: bad arguments");
   *host_ptr = nullptr;
   *dev_ptr = nullptr;
   void* p = nullptr;
   if (hipHostMalloc(&p, sizeof(int32_t) * (size_t)n, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess)
-    return err(MAPFX_ENOMEM, "hipHostMalloc (mapped, coherent) failed");
+    return perr(MAPFX_ENOMEM, "hipHostMalloc (mapped, coherent) failed");
   void* d = nullptr;
   if (hipHostGetDevicePointer(&d, p, 0) != hipSuccess) {
     (void)hipHostFree(p);
-    return err(MAPFX_EHIP, "hipHostGetDevicePointer failed");
+    return perr(MAPFX_EHIP, "hipHostGetDevicePointer failed");
   }
   memset(p, 0, sizeof(int32_t) * (size_t)n);
   *host_ptr = (int32_t*)p;

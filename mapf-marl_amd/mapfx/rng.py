@@ -1,6 +1,6 @@
 """Counter-based splitmix64 streams shared by the host (numpy) and the device.
 
-The device versions live in csrc/mapfx.hip (`splitmix64`, `gen_action`); the
+The device versions live in csrc/internal.h (`splitmix64`) and csrc/mapfx.hip (`gen_action`); the
 functions here are bit-identical numpy restatements used to build synthetic
 instances on the host and to check the device action generator.  Every stream
 is keyed by the GLOBAL env id, so an env's inputs do not depend on how envs are

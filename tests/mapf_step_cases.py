@@ -11,7 +11,7 @@ the non-square cases -- most of the table: a square map hides every H / W / pitc
 mix-up -- pin the kernels to the oracle's semantics only; tests/test_mapf_step_cases.py gives
 those expected values their second source, the Python restatement (oracle/mapf_oracle.py).
 
-`geometry` restates mapfx_create's layout sums, `dispatch` restates launch(), pick_wave_kernel
+`geometry` restates layout()'s sums, `dispatch` restates pick_wave(), launch(), pick_wave_kernel
 and pick_kernel; `expected_kernel` / `expected_action_path` answer for a case's launch.  A
 kernel comes back as (name, template arguments without spaces), the form `kernel_args`
 reduces a mapfx_last_kernel string to; the demangler prints every template argument, the
@@ -73,7 +73,7 @@ def _up(x, m):
 # --------------------------------------------------------------------------- geometry
 @functools.lru_cache(maxsize=None)
 def geometry(H, W, N, window=5, primal_size=10, obs_mode=OBS_WINDOW, rewards=DEFAULT_REWARDS):
-    """mapfx_create's sums (names as in csrc/mapfx.hip's Geo), or None where it refuses the
+    """layout()'s sums (names as in csrc/mapfx.hip's Geo), or None where mapfx_create refuses the
     configuration (one env over 160 KB of LDS)."""
     es = 1 if N <= 127 else 2                          # mapfx_obs_elem_size: bytes per cell
     L = 1
@@ -155,7 +155,7 @@ def _b(v):
 
 
 def dispatch(g, E, entry, T, outs, out_aligned=True, act="gen", act_aligned=True):
-    """launch() for one call: `entry` observe / step / rollout, `outs` the non-NULL outputs,
+    """pick_wave() and launch() for one call: `entry` observe / step / rollout, `outs` the non-NULL outputs,
     `out_aligned` every runner output pointer 16-byte aligned, `act` "gen" or the buffer's
     dtype, `act_aligned` its pointer 16-byte aligned.  Returns kernel, action_path and the
     intermediate decisions."""

@@ -10,7 +10,7 @@ semantics only.  Instances stay inside the reference's domain: one free componen
 agent starting on an obstacle.
 
 `expected_step_kernel`, `expected_bfs_kernel` and `expected_geometry` restate the host side
-of csrc/partial.hip (launch(), wg_apl, mapfx_partial_goal_dist, mapfx_partial_create's LDS
+of csrc/partial.hip (pick(), launch(), wg_apl, mapfx_partial_goal_dist, layout()'s LDS
 sums); the kernels come back as (name, template arguments without spaces), the form
 `kernel_args` reduces a mapfx_last_kernel string to.
 
@@ -45,7 +45,7 @@ KW = dict(move_reward=-0.01, stay_reward=-0.02, stay_goal_reward=0.5, node_colli
           gamma=0.99)
 STEPS = ((-1, 0), (1, 0), (0, -1), (0, 1))      # action 0 up, 1 down, 2 left, 3 right
 SIDES = ("top", "bottom", "left", "right")
-FAST_PAIRS = ((5, 16), (5, 8), (5, 32), (3, 16), (7, 16))     # (WIN, LF) of launch()
+FAST_PAIRS = ((5, 16), (5, 8), (5, 32), (3, 16), (7, 16))     # (WIN, LF) of pick()
 VARIANTS = 5          # distinct maps a per-env case cycles through
 
 
@@ -225,7 +225,7 @@ def family(c):
 
 
 def expected_step_kernel(c):
-    """launch(): the plain step's instance."""
+    """pick() / launch(): the plain step's instance."""
     fam = family(c)
     if fam == "workgroup":
         apl = -(-c.N // 256)                                    # wg_apl
@@ -263,7 +263,7 @@ def kernel_args(printed):
 
 
 def expected_geometry(c):
-    """mapfx_partial_create's sums for a case (anything with H, W, N, win, K): bytes per env,
+    """layout()'s sums (csrc/partial.hip) for a case (anything with H, W, N, win, K): bytes per env,
     envs per wave, the staging group (64: whole wave, 32: half waves, 0: rows stored
     straight to HBM), waves per block, a wave's LDS and whether the per-wave float32 sqrt
     table exists.  The workgroup path (big) keeps no map in LDS: EPW = wpb = 1."""

@@ -116,6 +116,45 @@ def test_create_rejects_out_of_range_configs():
 
     for kw, what in (({"n_envs": 1 << 26}, b"n_envs"), ({"n_envs": -1}, b"n_envs"),
                      ({"n_agents": 0}, b"n_agents"), ({"n_agents": 1025}, b"n_agents"),
-                     ({"H": 0}, b"grid"), ({"W": 4097}, b"grid")):
+                     ({"H": 0}, b"grid"), ({"W": 4097}, b"grid"),
+                     # 256 envs per block x 16 MB of map: the LDS sum passes 2^31 before the refusal
+                     ({"H": 4096, "W": 4096, "n_agents": 1}, b"one env needs")):
         rc, msg = create(**kw)
         assert rc == -1 and what in msg, (kw, rc, msg)
+
+
+def test_create_layout_matches_restated_geometry():
+    """mapfx_create's layout is a plain function of the configuration (csrc/mapfx.hip layout()),
+    and without a PRIMAL observation (no device LUT) and within 64 KB of LDS (no function
+    attribute) mapfx_create makes no HIP call that matters: for every distinct configuration
+    of the MAPF step cases, mapfx_query equals the restated geometry on the fields
+    tests/test_gpu_mapf_step_shapes.py compares -- here without a GPU, and with no launch."""
+    import ctypes
+    from mapf_step_cases import CASES, OBS_PRIMAL, case_geometry, limit_of, mode_of
+    from mapfx import lib
+    from mapfx._abi import Cfg, Info
+
+    configs = {}
+    for c in CASES:
+        configs.setdefault((c.H, c.W, c.N, c.window, c.psize, mode_of(c.obs), c.rewards), c)
+    checked = 0
+    for (H, W, N, window, psize, mode, rewards), c in configs.items():
+        g = case_geometry(c)
+        assert g is not None, c.name
+        if mode & OBS_PRIMAL or g.gen_lds > 64 * 1024:
+            continue
+        cfg = Cfg(H=H, W=W, n_agents=N, n_envs=c.E, env_offset=c.env_offset, episode_limit=limit_of(c),
+                  step_reward=rewards[0], collide_reward=rewards[1], obs_mode=mode, window=window,
+                  primal_size=psize, map_shared=0)
+        h = ctypes.c_void_p()
+        assert lib.mapfx_create(ctypes.byref(cfg), ctypes.byref(h)) == 0, (c.name, lib.mapfx_last_error())
+        try:
+            inf = Info()
+            assert lib.mapfx_query(h, ctypes.byref(inf)) == 0, c.name
+            got = {k: getattr(inf, k) for k, _ in Info._fields_}
+        finally:
+            lib.mapfx_destroy(h)
+        assert got == dict(lanes_per_env=g.L, agents_per_lane=g.apl, envs_per_block=g.EPB,
+                           block_threads=g.BT, lds_bytes=g.gen_lds, cell_bytes=g.es, pad=g.P), c.name
+        checked += 1
+    assert checked >= 140, (checked, len(configs))   # a skip rule cannot quietly empty the test

@@ -286,7 +286,7 @@ def test_occupancy_window(mapfx_mod):
 
 
 def _split_lds(s, n, win):
-    """LDS bytes of the split kernel without staged actions (mapfx_create / launch() in
+    """LDS bytes of the split kernel without staged actions (layout() / pick_wave() in
     mapfx.hip) for an s x s grid with n = 16 or 64 agents per env: per env of the wave the two
     count maps and the move map of the padded grid, the wave's two reward rows, the info
     and edge rings, the two store waves' staged records, the reward-code table and ring."""

@@ -27,7 +27,7 @@ rows, return and length are those of env b % P of the restatement run on the P
 archetypes, and the MAC's bs is every b whose b % P is in the restatement's bs.
 
 Which kernel a case reaches is asserted from mapfx_last_kernel after the run; the LDS
-geometry behind the staging classes (mapfx_partial_create's sums) is derived in
+geometry behind the staging classes (csrc/partial.hip layout()'s sums) is derived in
 CASES' comments.
 """
 import re
@@ -68,7 +68,7 @@ _OBS12 = ((2, 3), (5, 8), (9, 4), (7, 7))
 _OBS10 = ((3, 3), (6, 7))
 
 # name: grid, N, window, K, B, limit (T = limit + 1 <= 6), kernel = (name, template args)
-# launch() must pick; `tile`: B tiles that many archetype envs.
+# pick() must return; `tile`: B tiles that many archetype envs.
 #
 # LDS per env (mapfx_partial_create): 2 map images of rows * pitch bytes (rows = H + 2P,
 # pitch = round4(round4(P) + W + P), P = max(1, win / 2)) + the bitmap + L * 48 (features)

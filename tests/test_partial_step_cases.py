@@ -43,7 +43,7 @@ def test_kernel_args_reads_the_printed_form():
 
 
 def test_dispatch_rule_table():
-    """The rule on rows written out by hand (launch(), wg_apl, mapfx_partial_goal_dist)."""
+    """The rule on rows written out by hand (pick(), launch(), wg_apl, mapfx_partial_goal_dist)."""
     R = collections.namedtuple("R", "H W N win K")
     rows = [
         (R(32, 32, 16, 5, 5), ("partial_kernel", "5,5,16,2,false"), ("partial_bfs_kernel", "short")),
