@@ -175,6 +175,67 @@ typedef struct mapfx_partial_scen {
  * mapfx_partial_goal_dist on the same mask. */
 int mapfx_partial_draw(mapfx_partial_t* h, const mapfx_partial_scen* sc, void* stream);
 
+/* Fused multi-step rollout: T successive steps of all E envs in one call, with the
+ * actions given ([T][E][N]) or drawn by the on-device policy below.  Additive exports
+ * (the ABI version is unchanged).
+ *
+ * Trajectory arrays (device, caller-owned; NULL = not produced).  Slot k of each holds
+ * exactly what the k-th of T successive mapfx_partial_step calls writes to
+ * mapfx_partial_out; pos and terminated hold the state after that step.  After the call
+ * every array of `st` equals what those T calls leave, bit for bit (pdist, pnbr, node,
+ * edge and total_coll included). */
+typedef struct mapfx_partial_traj {
+  double*  reward;      /* [T][E]                     as mapfx_partial_out.reward   */
+  float*   obs;         /* [T][E][N][D]               NULL: rows are not even built */
+  float*   state;       /* [T][E][3]                                                */
+  uint8_t* avail;       /* [T][E][N]   5-bit mask of the post-step state            */
+  int32_t* pos;         /* [T][E][N][2] post-step (row, col)                        */
+  uint8_t* terminated;  /* [T][E]                                                   */
+  int8_t*  actions;     /* [T][E][N]   policy mode only: the action each agent took */
+  int32_t* err;         /* [1] as mapfx_partial_out.err, first report wins          */
+} mapfx_partial_traj;
+
+/* The on-device policy, used when `actions` is NULL: each agent walks down its own
+ * shortest path, with eps-random moves.  With gid = cfg.env_offset + e, step k of the
+ * call and agent a (splitmix64 and K_* as in mapfx_action, mapfx.h / mapfx/rng.py):
+ *
+ *   u = splitmix64(seed ^ gid*K_ENV ^ (t0 + k)*K_T ^ a*K_AGENT)     mapfx_action's word
+ *   (u >> 32) < eps_q :  act = u % 5                    == mapfx_action(seed, gid, t0+k, a)
+ *   otherwise         :  pd   = goal distance of the agent's cell in the pre-step state
+ *                        d_m  = goal distance of neighbour m (0 up, 1 down, 2 left, 3 right)
+ *                        ok_m = bit m of the PRE-step get_avail_actions mask and d_m >= 0
+ *                        pd < 0 or no ok_m with d_m < pd : act = 4 (stay)
+ *                        else act = the lowest m among the ok_m of minimal d_m
+ *
+ * eps_q runs over 0 .. 2^32: 0 is pure descent, 2^32 reproduces mapfx_action exactly.
+ * The action depends on (seed, gid, t0 + k, a) and the env's state only (shard-invariant);
+ * done agents get one by the same rule (the step ignores it).  The distances are the
+ * carried pdist / pnbr where they apply and looked up in goal_dist where they do not
+ * (pdist == INT32_MIN, pnbr == NULL).  mapfx.rng.partial_policy_actions restates the rule.
+ * Policy mode is offered where the wave kernel runs (N <= 64, sides <= 256) and the goal
+ * tables are u8 or int16 (H*W <= 32767); with int32 tables or on the workgroup path the
+ * call returns MAPFX_EINVAL. */
+typedef struct mapfx_partial_policy { uint64_t seed; uint64_t eps_q; int32_t t0; } mapfx_partial_policy;
+
+/* T steps.  `actions` [T][E][N] of action_dtype, or NULL to use `pol`.  An action
+ * outside 0..4 skips that env for that step only (env unchanged, reward 0.0, err set).
+ * autoreset != 0: at the start of every step k (k = 0 included) an env whose terminated
+ * flag is set is first reset exactly as mapfx_partial_reset resets a masked env, then
+ * stepped; starts and goals are not redrawn, so two calls of T/2 equal one of T.
+ * Asynchronous on `stream`, no allocation, no host sync (graph-capturable).
+ * MAPFX_EINVAL before any launch: T outside 1..65536, a bad action_dtype, actions and pol
+ * both NULL, policy mode where it is not offered.
+ * N <= 64 and sides <= 256: one launch of partial_rollout_kernel (state in registers,
+ * maps in LDS across the steps).  Otherwise (given actions only) the call enqueues T
+ * launches of the workgroup step kernel -- and the masked reset before each with
+ * autoreset -- with the same result; mapfx_partial_rollout_fused tells which. */
+int mapfx_partial_rollout(mapfx_partial_t* h, const mapfx_partial_state* st, int32_t T,
+                          const void* actions, int action_dtype,
+                          const mapfx_partial_policy* pol,
+                          int32_t autoreset, const mapfx_partial_traj* traj, void* stream);
+/* 1: one launch; 0: a loop of step launches */
+int mapfx_partial_rollout_fused(const mapfx_partial_t* h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,8 @@
 // Layout: one wavefront holds EPW envs (L = pow2ceil(N) lanes per env, lane =
 // agent); an env's padded cell map (c = count + 1 - obstacle, c == 0 blocked /
 // border) and its dep map (bit 7: obstacle, bits 0-6: the occupant's move) live in
-// LDS for the launch; state round-trips HBM between calls.  N > 64 or a side > 256
+// LDS for the launch; state round-trips HBM between calls (partial_rollout_kernel: T steps
+// of one launch, the state in registers and the maps in LDS in between).  N > 64 or a side > 256
 // (the reference's larger maps and agent counts) take partial_wg_kernel: one
 // workgroup per env, the agents' cells in an LDS hash table, the map in HBM.  Every fp64 value is
 // computed in the reference's operation order; the completion bonus comes from a host-libm
@@ -161,6 +162,20 @@ struct PArgs {
   const uint8_t* obs_mask;
   // the runner's fused actions (mapfx_partial_step_runner; act_row NULL otherwise)
   mapfx_runner_acts ra;
+};
+
+// partial_rollout_kernel (mapfx_partial_rollout): T steps of one launch.  PArgs' reward /
+// obs / state / avail point at slot 0 of the trajectory arrays; the kernel advances them.
+struct RArgs {
+  int T;
+  int autoreset;
+  int policy;           // actions from the on-device policy (PArgs.actions is then a dummy)
+  int t0;
+  uint64_t seed, eps_q;
+  long long env_offset;
+  int32_t* pos;         // [T][E][N][2], or NULL
+  uint8_t* terminated;  // [T][E], or NULL
+  int8_t* actions;      // [T][E][N] (policy mode), or NULL
 };
 
 // where env e's observation rows go ([N][D] floats), or nullptr when not written
@@ -1000,16 +1015,39 @@ __device__ __forceinline__ void runner_compact_block(const mapfx_runner_acts& ra
   }
 }
 
-template <int WIN, int KF, int LF, int GDE = 0, bool RUN = true>
-__global__ void __launch_bounds__(64 * PARTIAL_MAX_WPB) partial_kernel(PGeo g_, PArgs a) {
-  int blk = (int)blockIdx.x;
-  if constexpr (RUN) {  // the runner's fused compaction: the launch's extra first workgroup
-    if (a.ra.cmp_bs && blk-- == 0) {
-      extern __shared__ __align__(16) unsigned char lds_cmp[];
-      runner_compact_block(a.ra, lds_cmp);
-      return;
-    }
-  }
+// The on-device policy of mapfx_partial_rollout (mapfx_partial.h; mapfx/rng.py
+// partial_policy_actions restates it): mapfx_action's own word u decides between its
+// uniform draw ((u >> 32) < eps_q) and the descent of the agent's goal distances -- the
+// lowest-numbered available neighbour of minimal distance when that is below the cell's
+// own (pd), else stay.  avail: the PRE-step get_avail_actions mask; d0..d3: the goal
+// distances of the neighbours up, down, left, right (any value where the bit is clear).
+constexpr uint64_t PK_ENV = 0xD1B54A32D192ED03ull, PK_T = 0xABC98388FB8FAC03ull,
+                   PK_AGENT = 0x8CB92BA72F3D8DD7ull;  // mapfx/rng.py K_ENV, K_T, K_AGENT
+__device__ __forceinline__ int policy_action(const RArgs& ro, int env, int k, int ag, uint32_t avail, int pd,
+                                             int d0, int d1, int d2, int d3) {
+  const uint64_t u = splitmix64(ro.seed ^ ((uint64_t)(ro.env_offset + env) * PK_ENV) ^
+                                ((uint64_t)(uint32_t)(ro.t0 + k) * PK_T) ^ ((uint64_t)(uint32_t)ag * PK_AGENT));
+  if ((u >> 32) < ro.eps_q) return (int)(u % 5ull);
+  int best = 0x7FFFFFFF, bm = 4;
+  if ((avail & 1u) && d0 >= 0 && d0 < best) best = d0, bm = 0;
+  if ((avail & 2u) && d1 >= 0 && d1 < best) best = d1, bm = 1;
+  if ((avail & 4u) && d2 >= 0 && d2 < best) best = d2, bm = 2;
+  if ((avail & 8u) && d3 >= 0 && d3 < best) best = d3, bm = 3;
+  return (pd >= 0 && best < pd) ? bm : 4;
+}
+
+// The body of partial_kernel (ROLL 0: one pass, exactly the step / observe / reset kernel)
+// and of partial_rollout_kernel (ROLL 1: T steps with the observation rows, ROLL 2: T steps
+// without them -- no feature rows, no K-nearest rows, no window planes, no staging).  The
+// rollout keeps the agent state in registers and both maps in LDS between its steps, takes
+// a moving agent's npd (and the policy its four distances) from the neighbour lookups the
+// step issues anyway, and writes the state back once after the last step.  Its layout
+// (layout_rollout) keeps the staging images clear of live data, so nothing is rebuilt
+// between steps; stale low bits of dep are harmless: every occupant of a cell writes its
+// move before anyone reads it.
+template <int WIN, int KF, int LF, int GDE, bool RUN, int ROLL>
+__device__ __forceinline__ void partial_body(const PGeo& g_, const PArgs& a_, const RArgs& ro, const int blk) {
+  std::conditional_t<ROLL != 0, PArgs, const PArgs&> a = a_;  // (the rollout advances the outputs)
   PGeo g = g_;
   if constexpr (LF > 0) {  // the fast instances' lane group and K as constants (launch() picks
     g.L = LF;              // them only for g.L == LF, g.K == KF)
@@ -1090,7 +1128,7 @@ __global__ void __launch_bounds__(64 * PARTIAL_MAX_WPB) partial_kernel(PGeo g_, 
     epr_raw = a.ra.ep_return[ec_];
     epl_raw = a.ra.ep_length[ec_];
   }
-  if constexpr (KF > 0 && LF > 0) {  // float32 sqrt(0 .. sq_max) for the K-nearest rows
+  if constexpr (KF > 0 && LF > 0 && ROLL != 2) {  // float32 sqrt(0 .. sq_max) for the K-nearest rows
     if (g.off_sqrt >= 0) {            // (:352 math.sqrt), while the loads are in flight
       float* sqt = (float*)(lds + g.off_sqrt);
 #pragma unroll 1
@@ -1193,10 +1231,30 @@ __global__ void __launch_bounds__(64 * PARTIAL_MAX_WPB) partial_kernel(PGeo g_, 
   const bool nb_ok = nb_carry && a.do_step && pd != PD_NONE;
   const bool need_cur = has && (!a.do_step || !a.pdist || pd == PD_NONE);
   int npd_t = 0;
-  if (has && !nb_ok) {
-    const int tgt = (a.do_step && !dn) ? move_target(g, r, c, act) : -1;
-    if (tgt >= 0) npd_t = gd_entry_t<GDE>(g, a.gd, oa * g.hw + tgt);
-    if (need_cur) pd = gd_entry_t<GDE>(g, a.gd, oa * g.hw + r * g.W + c);
+  // the goal distances of the current cell's neighbours (up, down, left, right): the
+  // step's lookups for the next step; the rollout carries them from step to step
+  int nbd0 = 0, nbd1 = 0, nbd2 = 0, nbd3 = 0;
+  // the four neighbours of (r, c) from the table (an off-grid one: the cell itself)
+  const auto nbr_lookup = [&]() {
+    const long long gi = oc_ * g.hw + r * g.W + c;
+    nbd0 = gd_entry_t<GDE>(g, a.gd, gi + (r > 0 ? -g.W : 0));
+    nbd1 = gd_entry_t<GDE>(g, a.gd, gi + (r + 1 < g.H ? g.W : 0));
+    nbd2 = gd_entry_t<GDE>(g, a.gd, gi + (c > 0 ? -1 : 0));
+    nbd3 = gd_entry_t<GDE>(g, a.gd, gi + (c + 1 < g.W ? 1 : 0));
+  };
+  if constexpr (ROLL == 0) {
+    if (has && !nb_ok) {
+      const int tgt = (a.do_step && !dn) ? move_target(g, r, c, act) : -1;
+      if (tgt >= 0) npd_t = gd_entry_t<GDE>(g, a.gd, oa * g.hw + tgt);
+      if (need_cur) pd = gd_entry_t<GDE>(g, a.gd, oa * g.hw + r * g.W + c);
+    }
+  } else {  // once per launch: the carried distances, or the table where none apply
+    if (has && nb_ok) {
+      nbd0 = nbr_dist(nb0, 0), nbd1 = nbr_dist(nb0, 1), nbd2 = nbr_dist(nb0, 2), nbd3 = nbr_dist(nb0, 3);
+    } else if (has) {
+      if (need_cur) pd = gd_entry_t<GDE>(g, a.gd, oa * g.hw + r * g.W + c);
+      nbr_lookup();
+    }
   }
   PST(3);
   int cur = (r + g.P) * pitch + c + g.pl;
@@ -1204,6 +1262,89 @@ __global__ void __launch_bounds__(64 * PARTIAL_MAX_WPB) partial_kernel(PGeo g_, 
   wave_fence();
   PST(4);
 
+  // the rollout's given actions: row k + 1's block is fetched while step k runs -- an
+  // unconditional load (a conditional one compiles to a synchronous fetch), its row
+  // clamped below T
+  const long long act_row_bytes = (ROLL != 0 && ro.policy) ? 0 : ((long long)g.E * N) << esh;
+  uint2 araw_n = araw;
+  uintptr_t abyte_n = abyte;
+  const auto decode_raw = [&](uint2 raw, uintptr_t ab) {
+    const uint32_t w = (ab & 4) ? raw.y : raw.x;
+    if (a.act_dtype == MAPFX_I64) return act_decode((int)raw.x, (int)raw.y);
+    if (a.act_dtype == MAPFX_I32) return act_decode((int)w, (int)w >> 31);
+    const int v = (int)(int8_t)(uint8_t)(w >> ((ab & 3) * 8));
+    return act_decode(v, v >> 31);
+  };
+  // ---- state write-back (the step kernel: with its results; the rollout: after its loop) ----
+  const auto write_back = [&]() {
+    if (has) {
+      ((int2*)a.pos)[oa] = make_int2(r, c);
+      a.steps[oa] = steps;
+      a.at_goal[oa] = at_goal ? 1 : 0;
+      a.done[oa] = dn ? 1 : 0;
+      a.goal_cost[oa] = gcost;
+      a.node[oa] = (uint8_t)node;
+      a.edge[oa] = edge;
+      if (a.pdist) a.pdist[oa] = pd;
+      if (runner && arow >= 0) {  // the EpisodeBatch's actions / actions_onehot rows at ts
+        const long long v = act_value(alo, ahi);
+        if (a.ra.ep_actions)
+          a.ra.ep_actions[(long long)env * a.ra.ep_actions_sb + (long long)a.ra.ts * a.ra.ep_actions_st + ag] = v;
+        if (a.ra.ep_onehot) {
+          float* oh = a.ra.ep_onehot + (long long)env * a.ra.ep_onehot_sb +
+                      (long long)a.ra.ts * a.ra.ep_onehot_st + (long long)ag * 5;
+#pragma unroll
+          for (int q = 0; q < 5; ++q) oh[q] = v == q ? 1.0f : 0.0f;
+        }
+      }
+    }
+    if (env_ok && ag == 0) {
+      a.t[env] = tcur;
+      a.terminated[env] = term ? 1 : 0;
+      a.total_coll[env] = total;
+    }
+  };
+  const int T = ROLL ? ro.T : 1;
+  for (int k = 0; k < T; ++k) {  // (the step kernel: one pass, no loop is left in its code)
+  if constexpr (ROLL != 0) {
+    // autoreset: a terminated env restarts from init_pos (:125-163) before it is stepped
+    const bool rs = ro.autoreset && term;
+    if (__ballot(rs)) {
+      if (rs && has) atomicSub(&map32[cur >> 2], 1u << ((cur & 3) * 8));
+      if (rs) {
+        r = has ? ir : 0;
+        c = has ? ic : 0;
+        steps = 0, gcost = -1, edge = 0, node = 0;
+        at_goal = dn = term = false;
+        tcur = total = 0;
+        cur = (r + g.P) * pitch + c + g.pl;
+        if (has) {
+          atomicAdd(&map32[cur >> 2], 1u << ((cur & 3) * 8));
+          pd = gd_entry_t<GDE>(g, a.gd, oa * g.hw + r * g.W + c);
+          nbr_lookup();
+        }
+      }
+      wave_fence();
+    }
+    if (ro.policy) {
+      uint32_t pm = 16u;  // the pre-step avail mask, from the resident map
+      if (map[cur - pitch]) pm |= 1u;
+      if (map[cur + pitch]) pm |= 2u;
+      if (map[cur - 1]) pm |= 4u;
+      if (map[cur + 1]) pm |= 8u;
+      act = has ? policy_action(ro, env, k, ag, pm, pd, nbd0, nbd1, nbd2, nbd3) : 4;
+      if (has && ro.actions) ro.actions[(long long)k * g.E * N + oa] = (int8_t)act;
+    } else if (k > 0) {
+      act = has ? decode_raw(araw_n, abyte_n) : 4;
+    }
+    // (policy mode: row stride 0 -- the dummy block again, outside every branch)
+    // a GLOBAL load: a flat one also counts on the LDS counter, and the step's next LDS
+    // read would wait for it
+    abyte_n = abyte + (uintptr_t)(act_row_bytes * min(k + 1, T - 1));
+    typedef const unsigned long long __attribute__((address_space(1))) * GlobalU64;
+    const unsigned long long blk8 = *(GlobalU64)(abyte_n & ~(uintptr_t)7);
+    araw_n = make_uint2((uint32_t)blk8, (uint32_t)(blk8 >> 32));
+  }
   // ---- step (:165-310) ----
   double Rsum = 0.0;  // sum(rewards) of the env (agent-0 lane)
   if (a.do_step && env_ok) {
@@ -1240,7 +1381,9 @@ __global__ void __launch_bounds__(64 * PARTIAL_MAX_WPB) partial_kernel(PGeo g_, 
       }
       if (has) {                                            // :227-233
         const int opd = pd;
-        const int npd = moved ? (nb_ok ? nbr_dist(nb0, act) : npd_t) : opd;
+        int npd;
+        if constexpr (ROLL != 0) npd = moved ? (act == 0 ? nbd0 : act == 1 ? nbd1 : act == 2 ? nbd2 : nbd3) : opd;
+        else npd = moved ? (nb_ok ? nbr_dist(nb0, act) : npd_t) : opd;
         rew = rew + (double)(opd - npd) / (double)g.limit;
         pd = npd;
       }
@@ -1322,11 +1465,7 @@ __global__ void __launch_bounds__(64 * PARTIAL_MAX_WPB) partial_kernel(PGeo g_, 
   // neighbour the cell itself; no branch, so no use of a value can move up to its load)
   // (u8 tables, H * W <= 255: the 4 lookups of an agent fall in one 64-byte table, so one
   // memory request; int16 tables span two)
-  const long long gi = oc_ * g.hw + r * g.W + c;
-  const int nbd0 = gd_entry_t<GDE>(g, a.gd, gi + (r > 0 ? -g.W : 0));
-  const int nbd1 = gd_entry_t<GDE>(g, a.gd, gi + (r + 1 < g.H ? g.W : 0));
-  const int nbd2 = gd_entry_t<GDE>(g, a.gd, gi + (c > 0 ? -1 : 0));
-  const int nbd3 = gd_entry_t<GDE>(g, a.gd, gi + (c + 1 < g.W ? 1 : 0));
+  nbr_lookup();
 
   PST(8);
   // ---- the step's results leave before the observation rows are built: their stores
@@ -1347,32 +1486,11 @@ __global__ void __launch_bounds__(64 * PARTIAL_MAX_WPB) partial_kernel(PGeo g_, 
     a.state[3 * env + 1] = (float)tcur;
     a.state[3 * env + 2] = (float)gsum;
   }
-  // ---- state write-back ----
-  if (has) {
-    ((int2*)a.pos)[oa] = make_int2(r, c);
-    a.steps[oa] = steps;
-    a.at_goal[oa] = at_goal ? 1 : 0;
-    a.done[oa] = dn ? 1 : 0;
-    a.goal_cost[oa] = gcost;
-    a.node[oa] = (uint8_t)node;
-    a.edge[oa] = edge;
-    if (a.pdist) a.pdist[oa] = pd;
-    if (runner && arow >= 0) {  // the EpisodeBatch's actions / actions_onehot rows at ts
-      const long long v = act_value(alo, ahi);
-      if (a.ra.ep_actions)
-        a.ra.ep_actions[(long long)env * a.ra.ep_actions_sb + (long long)a.ra.ts * a.ra.ep_actions_st + ag] = v;
-      if (a.ra.ep_onehot) {
-        float* oh = a.ra.ep_onehot + (long long)env * a.ra.ep_onehot_sb +
-                    (long long)a.ra.ts * a.ra.ep_onehot_st + (long long)ag * 5;
-#pragma unroll
-        for (int k = 0; k < 5; ++k) oh[k] = v == k ? 1.0f : 0.0f;
-      }
-    }
-  }
-  if (env_ok && ag == 0) {
-    a.t[env] = tcur;
-    a.terminated[env] = term ? 1 : 0;
-    a.total_coll[env] = total;
+  if constexpr (ROLL == 0) {
+    write_back();
+  } else {  // the rollout's state stays in registers: its trajectory slots instead
+    if (has && ro.pos) ((int2*)ro.pos)[(long long)k * g.E * N + oa] = make_int2(r, c);
+    if (env_ok && ag == 0 && ro.terminated) ro.terminated[(long long)k * g.E + env] = term ? 1 : 0;
   }
   if (post && env_ok) {  // runner_post_kernel (runner.hip) for a running env, fused
     const mapfx_runner_acts& ra = a.ra;
@@ -1403,6 +1521,8 @@ __global__ void __launch_bounds__(64 * PARTIAL_MAX_WPB) partial_kernel(PGeo g_, 
     // fused (cmp_bs), A[(ts + 1) & 1] = running after this step, written for every env
     if (ag == 0) ra.alive_prev[env] = ra.cmp_bs ? (uint8_t)(live0 && !term ? 1 : 0) : live0;
   }
+  uint2 nb1 = make_uint2(0u, 0u);
+  if constexpr (ROLL != 2) {  // (a rollout without the rows builds and stages none of this)
   // ---- observations of the current state (:312-391) ----
   // per-agent feature rows: curr, start, goal, unit vec, norm, node, edge, steps
   if (has) {
@@ -1608,9 +1728,11 @@ __global__ void __launch_bounds__(64 * PARTIAL_MAX_WPB) partial_kernel(PGeo g_, 
   }
   PST(10);
   // the carried neighbour distances (their loads have landed by now)
-  uint2 nb1 = make_uint2(((uint32_t)nbd0 & 0xFFFFu) | ((uint32_t)nbd1 << 16),
-                         ((uint32_t)nbd2 & 0xFFFFu) | ((uint32_t)nbd3 << 16));
-  asm volatile("" : "+v"(nb1.x), "+v"(nb1.y));
+  if constexpr (ROLL == 0) {
+    nb1 = make_uint2(((uint32_t)nbd0 & 0xFFFFu) | ((uint32_t)nbd1 << 16),
+                     ((uint32_t)nbd2 & 0xFFFFu) | ((uint32_t)nbd3 << 16));
+    asm volatile("" : "+v"(nb1.x), "+v"(nb1.y));
+  }
   if constexpr (FAST) {
     if (g.off_stage < 0 && has && my_obs) {  // rows straight to HBM (per-lane stores)
       uint32_t* d = (uint32_t*)(my_obs + ag * DF);
@@ -1633,14 +1755,49 @@ __global__ void __launch_bounds__(64 * PARTIAL_MAX_WPB) partial_kernel(PGeo g_, 
   }
   PST(11);
   (void)o;
-  // the carried neighbour distances are stored last (their loads land during the rows)
-  if (has && nb_carry) ((uint2*)a.pnbr)[oa] = nb1;
+  }
+  if constexpr (ROLL == 0) {
+    // the carried neighbour distances are stored last (their loads land during the rows)
+    if (has && nb_carry) ((uint2*)a.pnbr)[oa] = nb1;
+  } else {  // the next step's slots
+    if (a.reward) a.reward += g.E;
+    if (a.obs) a.obs += (long long)g.E * N * g.D;
+    if (a.state) a.state += 3ll * g.E;
+    if (a.avail) a.avail += (long long)g.E * N;
+  }
+  }  // for k
+  if constexpr (ROLL != 0) {  // the state leaves once, after the last step
+    write_back();
+    if (has && nb_carry)
+      ((uint2*)a.pnbr)[oa] = make_uint2(((uint32_t)nbd0 & 0xFFFFu) | ((uint32_t)nbd1 << 16),
+                                        ((uint32_t)nbd2 & 0xFFFFu) | ((uint32_t)nbd3 << 16));
+  }
   PST(12);
 #ifdef PARTIAL_STAMPS
   __builtin_amdgcn_s_waitcnt(0);
   PST(13);
   PST_FLUSH();
 #endif
+}
+
+template <int WIN, int KF, int LF, int GDE = 0, bool RUN = true>
+__global__ void __launch_bounds__(64 * PARTIAL_MAX_WPB) partial_kernel(PGeo g_, PArgs a) {
+  int blk = (int)blockIdx.x;
+  if constexpr (RUN) {  // the runner's fused compaction: the launch's extra first workgroup
+    if (a.ra.cmp_bs && blk-- == 0) {
+      extern __shared__ __align__(16) unsigned char lds_cmp[];
+      runner_compact_block(a.ra, lds_cmp);
+      return;
+    }
+  }
+  partial_body<WIN, KF, LF, GDE, RUN, 0>(g_, a, RArgs{}, blk);
+}
+
+// T steps of every env in one launch (mapfx_partial_rollout).  OBS false: the trajectory
+// has no observation rows, and WIN / KF play no part.
+template <int WIN, int KF, int LF, int GDE, bool OBS>
+__global__ void __launch_bounds__(64 * PARTIAL_MAX_WPB) partial_rollout_kernel(PGeo g_, PArgs a, RArgs ro) {
+  partial_body<WIN, KF, LF, GDE, false, OBS ? 1 : 2>(g_, a, ro, (int)blockIdx.x);
 }
 
 // A goal-table rebuild makes the carried distances stale: pdist of every (masked) env
@@ -1774,6 +1931,7 @@ __global__ void __launch_bounds__(256) sqrt_probe_kernel(double* out, int n) {
 struct mapfx_partial_t {
   mapfx_partial_cfg cfg;
   PGeo geo;
+  PGeo geo_roll[2];  // partial_rollout_kernel's: [0] without the observation rows, [1] with (layout_rollout)
   double* bonus_lut;
   int device;
   int no_nbcarry;  // diagnostic builds (MAPFX_PARTIAL_DIAG_ENV) only: ignore the state's pnbr
@@ -1842,6 +2000,65 @@ PartialFn pick(int win, int K, int L, int tw, bool run) {
     case 9: return partial_kernel<9, 0, 0>;
   }
   return nullptr;
+}
+
+// partial_rollout_kernel's instances: with the rows one per partial_kernel shape (the 15
+// fast ones, the six generic windows); without them the window and K play no part: one per
+// fast lane group and table width, and one generic.
+using RolloutFn = void (*)(PGeo, PArgs, RArgs);
+template <int WIN, int LF, bool OBS>
+RolloutFn pick_roll_fast(int tw) {
+  return tw == 1 ? partial_rollout_kernel<WIN, 5, LF, 1, OBS> : tw == 2 ? partial_rollout_kernel<WIN, 5, LF, 2, OBS>
+                                                                        : partial_rollout_kernel<WIN, 5, LF, 0, OBS>;
+}
+RolloutFn pick_roll(int win, int K, int L, int tw, bool obs) {
+  if (!obs) {
+    if (L == 8) return pick_roll_fast<0, 8, false>(tw);
+    if (L == 16) return pick_roll_fast<0, 16, false>(tw);
+    if (L == 32) return pick_roll_fast<0, 32, false>(tw);
+    return partial_rollout_kernel<0, 0, 0, 0, false>;
+  }
+  if (K == 5 && win == 5 && L == 16) return pick_roll_fast<5, 16, true>(tw);
+  if (K == 5 && win == 5 && L == 8) return pick_roll_fast<5, 8, true>(tw);
+  if (K == 5 && win == 5 && L == 32) return pick_roll_fast<5, 32, true>(tw);
+  if (K == 5 && win == 3 && L == 16) return pick_roll_fast<3, 16, true>(tw);
+  if (K == 5 && win == 7 && L == 16) return pick_roll_fast<7, 16, true>(tw);
+  switch (win) {
+    case 0: return partial_rollout_kernel<0, 0, 0, 0, true>;
+    case 1: return partial_rollout_kernel<1, 0, 0, 0, true>;
+    case 3: return partial_rollout_kernel<3, 0, 0, 0, true>;
+    case 5: return partial_rollout_kernel<5, 0, 0, 0, true>;
+    case 7: return partial_rollout_kernel<7, 0, 0, 0, true>;
+    case 9: return partial_rollout_kernel<9, 0, 0, 0, true>;
+  }
+  return nullptr;
+}
+
+// The rollout's layout of a wave-kernel configuration: layout()'s regions, with the staging
+// images BEHIND them instead of over the dep map onwards -- a loop of steps reads bit 7 of
+// every dep byte (the obstacle flag) and the sqrt table again after the rows have left.
+// Without the rows (obs false) there is no staging and no sqrt table.
+void layout_rollout(const PGeo& base, bool obs, PGeo& g) {
+  g = base;
+  int off = g.off_rew + g.EPW * g.rew_env_bytes;
+  if (obs && g.off_sqrt >= 0) off = g.off_sqrt + round_up((g.sq_max + 1) * 4, 16);
+  if (!obs) g.off_sqrt = -1;
+  g.off_stage = -1;
+  g.stage_lanes = 0;
+  if (obs && g.K == 5 && (g.win == 3 || g.win == 5 || g.win == 7) && g.L >= 8 && g.L <= 32) {
+    for (int G : {64, 32}) {
+      const int need = off + std::min(g.EPW, G / g.L) * g.stage_env_bytes;
+      if (need <= (G == 64 ? 40 * 1024 : 64 * 1024)) {
+        g.off_stage = off;
+        g.stage_lanes = G;
+        off = need;
+        break;
+      }
+    }
+  }
+  g.lds = round_up(off, 16);
+  g.wpb = PARTIAL_MAX_WPB;
+  while (g.wpb > 1 && g.wpb * g.lds > 160 * 1024) --g.wpb;
 }
 
 int launch(mapfx_partial_t* h, PArgs& a, void* stream) {
@@ -2082,6 +2299,17 @@ int mapfx_partial_create(const mapfx_partial_cfg* cfg, mapfx_partial_t** out) {
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, g.lds * g.wpb),
                              "hipFuncSetAttribute(partial_kernel LDS)");
   }
+  if (!g.big) {  // the rollout's two layouts and this configuration's two instances
+    for (int obs = 0; obs < 2 && !rc; ++obs) {
+      PGeo& gr = h->geo_roll[obs];
+      layout_rollout(g, obs != 0, gr);
+      const RolloutFn fn = pick_roll(g.win, g.K, g.L, g.gd8 ? 1 : g.gd32 ? 0 : 2, obs != 0);
+      if (fn && gr.lds * gr.wpb > 64 * 1024)
+        rc = check_hip(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           gr.lds * gr.wpb),
+                       "hipFuncSetAttribute(partial_rollout_kernel LDS)");
+    }
+  }
   if (rc) return rc;
   {  // the map build's multiply-high division (partial_kernel) must be exact on its range
     const unsigned long long nw = (unsigned long long)g.rows * g.wpr;
@@ -2282,6 +2510,97 @@ int mapfx_partial_observe(mapfx_partial_t* h, const mapfx_partial_state* st,
   fill_out(a, out);
   a.reward = nullptr;
   return launch(h, a, stream);
+}
+
+int mapfx_partial_rollout_fused(const mapfx_partial_t* h) { return h && !h->geo.big ? 1 : 0; }
+
+int mapfx_partial_rollout(mapfx_partial_t* h, const mapfx_partial_state* st, int32_t T, const void* actions,
+                          int action_dtype, const mapfx_partial_policy* pol, int32_t autoreset,
+                          const mapfx_partial_traj* traj, void* stream) {
+  if (!h) return perr(MAPFX_EINVAL, "NULL handle");
+  int rc = check_state(h, st);
+  if (rc) return rc;
+  if (T < 1 || T > 65536) return perr(MAPFX_EINVAL, "mapfx_partial_rollout: T must be in 1..65536");
+  if (action_dtype < MAPFX_I8 || action_dtype > MAPFX_I64) return perr(MAPFX_EINVAL, "bad action_dtype");
+  if (!actions && !pol) return perr(MAPFX_EINVAL, "mapfx_partial_rollout: actions or a policy is required");
+  const PGeo& g = h->geo;
+  const bool policy = actions == nullptr;
+  if (policy && (g.big || g.gd32))
+    return perr(MAPFX_EINVAL,
+                "mapfx_partial_rollout: the on-device policy needs the wave kernel (N <= 64, sides <= 256) "
+                "and u8 / int16 goal tables (H * W <= 32767)");
+  if (g.E == 0) return MAPFX_OK;
+  const mapfx_partial_traj none = {};
+  const mapfx_partial_traj& tj = traj ? *traj : none;
+  const long long EN = (long long)g.E * g.N;
+  PArgs a;
+  memset(&a, 0, sizeof(a));
+  fill_state(a, st);
+  a.act_dtype = action_dtype;
+  a.do_step = 1;
+  a.err = tj.err;
+  if (g.big) {
+    // the workgroup path: T step launches with the slot pointers advanced (and the masked
+    // reset before each when autoreset), the post-step positions and flags copied to
+    // their slots -- the same result, one launch floor per step
+    const hipStream_t sm = (hipStream_t)stream;
+    const size_t esz = action_dtype == MAPFX_I64 ? 8 : action_dtype == MAPFX_I32 ? 4 : 1;
+    for (int k = 0; k < T && !rc; ++k) {
+      if (autoreset) {
+        PArgs r = a;
+        r.do_step = 0;
+        r.do_reset = 1;
+        r.reset_mask = st->terminated;
+        r.err = nullptr;
+        rc = launch(h, r, stream);
+        if (rc) break;
+      }
+      PArgs s = a;
+      s.actions = (const char*)actions + (size_t)k * EN * esz;
+      s.reward = tj.reward ? tj.reward + (long long)k * g.E : nullptr;
+      s.obs = tj.obs ? tj.obs + k * EN * g.D : nullptr;
+      s.state = tj.state ? tj.state + 3ll * k * g.E : nullptr;
+      s.avail = tj.avail ? tj.avail + k * EN : nullptr;
+      rc = launch(h, s, stream);
+      if (!rc && tj.pos)
+        rc = check_hip(hipMemcpyAsync(tj.pos + k * EN * 2, st->pos, sizeof(int32_t) * 2 * EN,
+                                      hipMemcpyDeviceToDevice, sm), "hipMemcpyAsync(traj pos)");
+      if (!rc && tj.terminated)
+        rc = check_hip(hipMemcpyAsync(tj.terminated + (long long)k * g.E, st->terminated, (size_t)g.E,
+                                      hipMemcpyDeviceToDevice, sm), "hipMemcpyAsync(traj terminated)");
+    }
+    return rc;
+  }
+  const bool obs = tj.obs != nullptr;
+  const RolloutFn fn = pick_roll(g.win, g.K, g.L, g.gd8 ? 1 : g.gd32 ? 0 : 2, obs);
+  if (!fn) return perr(MAPFX_EINVAL, "obs_window must be one of 0, 1, 3, 5, 7, 9");
+  a.bonus_lut = h->bonus_lut;
+  if (h->no_nbcarry) a.pnbr = nullptr;
+  // policy mode: the prologue's unconditional action load reads the positions instead
+  a.actions = policy ? (const void*)st->pos : actions;
+  if (policy) a.act_dtype = MAPFX_I8;
+  a.reward = tj.reward;
+  a.obs = tj.obs;
+  a.state = tj.state;
+  a.avail = tj.avail;
+  RArgs ro;
+  memset(&ro, 0, sizeof(ro));
+  ro.T = T;
+  ro.autoreset = autoreset ? 1 : 0;
+  ro.policy = policy ? 1 : 0;
+  if (policy) {
+    ro.t0 = pol->t0;
+    ro.seed = pol->seed;
+    ro.eps_q = pol->eps_q;
+    ro.actions = tj.actions;
+  }
+  ro.env_offset = (long long)h->cfg.env_offset;
+  ro.pos = tj.pos;
+  ro.terminated = tj.terminated;
+  const PGeo& gr = h->geo_roll[obs ? 1 : 0];
+  const int waves = (g.E + gr.EPW - 1) / gr.EPW;
+  return launch_kernel(fn, dim3((waves + gr.wpb - 1) / gr.wpb), dim3(64 * gr.wpb), gr.lds * gr.wpb,
+                       (hipStream_t)stream, nullptr, nullptr, "partial_rollout_kernel launch", NOTED, gr, a, ro);
 }
 
 }  // extern "C"

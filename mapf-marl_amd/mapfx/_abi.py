@@ -76,6 +76,15 @@ class PScen(ctypes.Structure):  # include/mapfx_partial.h mapfx_partial_scen
                 ("mask", c_vp), ("err", c_vp)]
 
 
+class PTraj(ctypes.Structure):  # include/mapfx_partial.h mapfx_partial_traj
+    _fields_ = [(k, c_vp) for k in ("reward", "obs", "state", "avail", "pos", "terminated",
+                                    "actions", "err")]
+
+
+class PPolicy(ctypes.Structure):  # include/mapfx_partial.h mapfx_partial_policy
+    _fields_ = [("seed", c_u64), ("eps_q", c_u64), ("t0", c_i32)]
+
+
 class QCfg(ctypes.Structure):  # include/mapfx_primal.h
     _fields_ = [(k, c_i32) for k in ("H", "W", "n_agents", "n_envs", "obs_size", "map_shared",
                                      "diagonal")]
@@ -108,7 +117,8 @@ EXPORTS = ("mapfx_abi_version", "mapfx_last_error", "mapfx_build_id", "mapfx_las
            "mapfx_partial_create", "mapfx_partial_destroy", "mapfx_partial_obs_dim",
            "mapfx_partial_goal_dist_elem_size",
            "mapfx_partial_goal_dist", "mapfx_partial_reset", "mapfx_partial_step",
-           "mapfx_partial_observe", "mapfx_partial_draw", "mapfx_primal_create", "mapfx_primal_destroy",
+           "mapfx_partial_observe", "mapfx_partial_draw", "mapfx_partial_rollout",
+           "mapfx_partial_rollout_fused", "mapfx_primal_create", "mapfx_primal_destroy",
            "mapfx_primal_act", "mapfx_primal_act_timed", "mapfx_primal_observe",
            "mapfx_primal_blocking_count",
            "mapfx_primal_blocking", "mapfx_primal_generate", "mapfx_runner_begin", "mapfx_runner_actions", "mapfx_runner_post",
@@ -171,6 +181,9 @@ def _load():
         "mapfx_partial_step": (c_i32, [c_vp, P(PState), c_vp, c_i32, P(POut), c_vp]),
         "mapfx_partial_observe": (c_i32, [c_vp, P(PState), P(POut), c_vp]),
         "mapfx_partial_draw": (c_i32, [c_vp, P(PScen), c_vp]),
+        "mapfx_partial_rollout": (c_i32, [c_vp, P(PState), c_i32, c_vp, c_i32, P(PPolicy), c_i32,
+                                          P(PTraj), c_vp]),
+        "mapfx_partial_rollout_fused": (c_i32, [c_vp]),
         "mapfx_primal_create": (c_i32, [P(QCfg), P(c_vp)]),
         "mapfx_primal_destroy": (None, [c_vp]),
         "mapfx_primal_act": (c_i32, [c_vp, P(QState), c_vp, c_vp, c_i32, P(QOut), c_vp]),

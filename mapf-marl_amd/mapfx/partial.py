@@ -231,6 +231,85 @@ class MarlPartialBatch:
                          _DTYPES[a.dtype], ctypes.byref(self._out)), "mapfx_partial_step")
         return self.out
 
+    TRAJ_KEYS = ("reward", "obs", "state", "avail", "pos", "terminated", "actions")
+
+    def rollout_fused(self):
+        """True: `rollout` is one launch (the wave kernel); False: a loop of step launches
+        (N > 64 or a side > 256)."""
+        return bool(lib.mapfx_partial_rollout_fused(self._h))
+
+    def _traj_spec(self, T, obs, policy):
+        E, N = self.E, self.N
+        spec = {"reward": ((T, E), torch.float64), "state": ((T, E, 3), torch.float32),
+                "avail": ((T, E, N), torch.uint8), "pos": ((T, E, N, 2), torch.int32),
+                "terminated": ((T, E), torch.uint8)}
+        if obs:
+            spec["obs"] = ((T, E, N, self.obs_dim), torch.float32)
+        if policy:
+            spec["actions"] = ((T, E, N), torch.int8)
+        return spec
+
+    def rollout(self, actions=None, T=None, *, eps=None, seed=0, t0=0, autoreset=False, obs=True,
+                out=None):
+        """T steps in one call (mapfx_partial_rollout; one launch where `rollout_fused()`).
+
+        actions: [T, E, N] int8 / int32 / int64 -- or actions=None with T and eps (a float in
+        0..1, mapped to eps_q = round(eps * 2**32), or an int eps_q in 0..2**32): the
+        on-device policy (rng.partial_policy_actions: shortest-path descent with eps-random
+        moves keyed by (seed, global env, t0 + k, agent)).  autoreset: an env whose
+        terminated flag is set restarts from init_pos before it is stepped.  Returns a dict
+        of trajectory tensors whose slot k is what the k-th of T `step` calls returns --
+        reward [T, E], obs [T, E, N, D] (absent and not built with obs=False), state, avail,
+        pos and terminated after that step, actions in policy mode -- allocated once per
+        (T, obs, mode) and reused, or the caller's own `out` (the same keys; a missing one
+        is not produced)."""
+        policy = actions is None
+        if policy:
+            if T is None or eps is None:
+                raise ValueError("rollout needs actions, or T and eps for the on-device policy")
+            T = int(T)
+            if isinstance(eps, (int, np.integer)) and not isinstance(eps, bool):
+                eps_q = int(eps)
+            else:
+                if not 0.0 <= float(eps) <= 1.0:
+                    raise ValueError("eps must be a float in 0..1 or an int eps_q in 0..2**32")
+                eps_q = int(round(float(eps) * 2 ** 32))
+            if not 0 <= eps_q <= 2 ** 32:
+                raise ValueError("eps_q must be in 0..2**32")
+            a, dt = None, MAPFX_I8
+            pol = _abi.PPolicy(seed=int(seed) & 0xFFFFFFFFFFFFFFFF, eps_q=eps_q, t0=int(t0))
+        else:
+            a = torch.as_tensor(actions, device=self.device)
+            if a.dtype not in _DTYPES:
+                a = a.to(torch.int64)
+            a = a.contiguous()
+            if a.dim() != 3 or tuple(a.shape[1:]) != (self.E, self.N) or \
+                    (T is not None and int(T) != a.shape[0]):
+                raise AssertionError("actions must be [T, %d, %d]" % (self.E, self.N))
+            T, dt, pol = int(a.shape[0]), _DTYPES[a.dtype], None
+        spec = self._traj_spec(T, obs, policy)
+        if out is None:
+            cache = self.__dict__.setdefault("_traj_cache", {})
+            key = (T, bool(obs), policy)
+            if key not in cache:
+                cache[key] = {k: torch.zeros(shape, dtype=d, device=self.device)
+                              for k, (shape, d) in spec.items()}
+            out = cache[key]
+        else:
+            for k, t in out.items():
+                if k not in spec:
+                    raise AssertionError("rollout: no trajectory array %r in this mode" % (k,))
+                shape, d = spec[k]
+                if tuple(t.shape) != shape or t.dtype != d or not t.is_contiguous() or \
+                        t.device != self.pos.device:
+                    raise AssertionError("out[%r] must be a contiguous %s %s on %s"
+                                         % (k, d, list(shape), self.pos.device))
+        traj = _abi.PTraj(err=ptr(self.err), **{k: ptr(out.get(k)) for k in self.TRAJ_KEYS})
+        check(self._call(lib.mapfx_partial_rollout, self._h, ctypes.byref(self._state), T, ptr(a), dt,
+                         ctypes.byref(pol) if pol is not None else None, 1 if autoreset else 0,
+                         ctypes.byref(traj)), "mapfx_partial_rollout")
+        return out
+
     def host_mirror(self):
         """Pinned host copy of the packed buffer and its typed views (packed=True)."""
         if not self.packed:

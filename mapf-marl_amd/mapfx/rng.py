@@ -53,6 +53,37 @@ def gen_actions(seed, env_ids, t_ids, n_agents):
     return (splitmix64(k) % np.uint64(5)).astype(np.int8)
 
 
+def partial_policy_actions(seed, env_ids, t, eps_q, avail, pd, d):
+    """The on-device policy of mapfx_partial_rollout (include/mapfx_partial.h), restated for
+    one step.
+
+    u = splitmix64(seed ^ gid*K_ENV ^ t*K_T ^ a*K_AGENT) is `gen_actions`' own word: where
+    (u >> 32) < eps_q the action is u % 5 (eps_q = 2**32: gen_actions exactly); elsewhere the
+    agent descends its goal distances: with ok_m = bit m of the PRE-step avail mask and
+    d[m] >= 0, it stays (4) when pd < 0 or no ok_m has d[m] < pd, else takes the lowest m
+    among the ok_m of minimal d[m].
+
+    env_ids [E] global env ids, t the step's counter (t0 + k), avail [E, N] 5-bit masks,
+    pd [E, N] the goal distance of each agent's cell, d [E, N, 4] those of its neighbours
+    (up, down, left, right; any value where the avail bit is clear).  Returns int8 [E, N].
+    """
+    avail = np.asarray(avail, dtype=np.int64)
+    pd = np.asarray(pd, dtype=np.int64)
+    d = np.asarray(d, dtype=np.int64)
+    E, N = pd.shape
+    env = np.asarray(env_ids, dtype=np.int64).astype(np.uint64)[:, None]
+    ag = np.arange(N, dtype=np.uint64)[None, :]
+    tt = np.uint64(int(t) & 0xFFFFFFFF)
+    u = splitmix64(np.uint64(seed) ^ _mul(env, K_ENV) ^ _mul(tt, K_T) ^ _mul(ag, K_AGENT))
+    explore = (u >> np.uint64(32)) < np.uint64(eps_q)               # eps_q may be 2**32
+    ok = (((avail[..., None] >> np.arange(4)) & 1) == 1) & (d >= 0)
+    big = np.iinfo(np.int64).max
+    dm = np.where(ok, d, big)
+    best = dm.min(-1)
+    greedy = np.where((pd >= 0) & (best < pd), dm.argmin(-1), 4)    # argmin: the lowest m of a tie
+    return np.where(explore, (u % np.uint64(5)).astype(np.int64), greedy).astype(np.int8)
+
+
 def cell_keys(seed, env_ids, n_cells, stream):
     """Per-(env, cell) uint64 keys of stream `stream` (obstacles, starts, goals)."""
     env = np.asarray(env_ids, dtype=np.int64).astype(np.uint64)[:, None]
