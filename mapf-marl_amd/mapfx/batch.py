@@ -10,25 +10,19 @@ from __future__ import annotations
 
 import ctypes
 
-import numpy as np
 import torch
 
 from . import _abi
-from ._abi import MAPFX_I8, MAPFX_I32, MAPFX_I64, MAPFX_OBS_FULL, MAPFX_OBS_PRIMAL, \
-    MAPFX_OBS_WINDOW, check, lib, ptr
-from .maps import map_stride, pack_bits
+from ._abi import MAPFX_I8, MAPFX_OBS_FULL, MAPFX_OBS_PRIMAL, MAPFX_OBS_WINDOW, check, lib, ptr
+from ._base import DeviceBatch, as_actions, avail_bits, check_on_grid, parse_agents, parse_map, u64
+from ._base import env_mask as _env_mask    # (the methods' own `env_mask` argument hides it)
 
-_DTYPES = {torch.int8: MAPFX_I8, torch.int32: MAPFX_I32, torch.int64: MAPFX_I64}
 OBS_MODES = {"full": MAPFX_OBS_FULL, "window": MAPFX_OBS_WINDOW, "window_occ": MAPFX_OBS_WINDOW,
              "primal": MAPFX_OBS_PRIMAL}
 _OBS_KEYS = ("term", "avail", "obs_full", "obs_window", "obs_window_occ", "obs_primal", "primal_vec")
 
 
-def _stream_handle() -> int:
-    return torch.cuda.current_stream().cuda_stream
-
-
-class MapfGridBatch:
+class MapfGridBatch(DeviceBatch):
     """E independent MAPF_GRID envs on one GPU.
 
     Parameters mirror MAPF_GRID.__init__ (envs/mapf_gridworld.py:21-32) plus the
@@ -44,33 +38,11 @@ class MapfGridBatch:
     def __init__(self, init_pos, goals, grids=None, bits=None, hw=None, episode_limit=10000,
                  step_reward=-0.01, collide_reward=-10, obs=("full",), window=5,
                  primal_size=10, device=None, env_offset=0, track_steps=True, packed=False):
-        self.device = torch.device(device if device is not None else "cuda")
-        if self.device.type != "cuda":
-            raise RuntimeError("MapfGridBatch runs on a HIP device only (got %s)" % self.device)
-        init_pos = torch.as_tensor(np.array(init_pos, dtype=np.int32))
-        goals = torch.as_tensor(np.array(goals, dtype=np.int32))
-        if init_pos.ndim != 3 or init_pos.shape[-1] != 2 or goals.shape != init_pos.shape:
-            raise ValueError("init_pos/goals must both be [E, N, 2]")
-        self.E, self.N = int(init_pos.shape[0]), int(init_pos.shape[1])
-        if bits is None:
-            g = np.asarray(grids)
-            if g.ndim == 2:
-                g = g[None]
-            self.H, self.W = int(g.shape[1]), int(g.shape[2])
-            bits = pack_bits(g)
-        else:
-            self.H, self.W = hw
-        bits = np.array(bits, dtype=np.uint8)
-        if bits.ndim == 1:
-            bits = bits[None]
-        if bits.shape[1] != map_stride(self.H, self.W) or bits.shape[0] not in (1, self.E):
-            raise ValueError("bits must be [E or 1, %d]" % map_stride(self.H, self.W))
-        ip, gl = init_pos.numpy(), goals.numpy()
-        for name, arr in (("init_pos", ip), ("goals", gl)):
-            if arr.size and (arr[..., 0].min() < 0 or arr[..., 0].max() >= self.H
-                             or arr[..., 1].min() < 0 or arr[..., 1].max() >= self.W):
-                raise ValueError("%s outside the %dx%d grid" % (name, self.H, self.W))
-        self.map_shared = bits.shape[0] == 1 and self.E != 1
+        super().__init__(device)
+        self.E, self.N, init_pos, goals = parse_agents(init_pos, goals, "init_pos/goals")
+        self.H, self.W, bits, self.map_shared = parse_map(grids, bits, hw, self.E)
+        check_on_grid(init_pos, self.H, self.W, "init_pos")
+        check_on_grid(goals, self.H, self.W, "goals")
         self.episode_limit = int(episode_limit)
         self.step_reward = step_reward
         self.collide_reward = collide_reward
@@ -86,47 +58,28 @@ class MapfGridBatch:
                        obs_mode=mode, window=self.window, primal_size=self.primal_size,
                        map_shared=1 if self.map_shared else 0)
         self._cfg = cfg
-        with torch.cuda.device(self.device):
-            h = ctypes.c_void_p()
-            check(lib.mapfx_create(ctypes.byref(cfg), ctypes.byref(h)), "mapfx_create")
-        self._h = h
+        self._create(lib.mapfx_create, lib.mapfx_destroy, cfg)
         dev = self.device
         self.bits = torch.as_tensor(bits).to(dev)
-        self.init_pos = init_pos.to(dev).contiguous()
-        self.goal = goals.to(dev).contiguous()
+        self.init_pos = torch.as_tensor(init_pos).to(dev).contiguous()
+        self.goal = torch.as_tensor(goals).to(dev).contiguous()
         self.obs_elem = torch.int8 if lib.mapfx_obs_elem_size(self.N) == 1 else torch.int16
         self.edge_elem = torch.uint8 if lib.mapfx_edge_elem_size(self.N) == 1 else torch.int16  # counts < 2^15
-        self.err = torch.zeros((1,), dtype=torch.int32, device=dev)
         # `packed`: the mutable state and every per-step output are views of ONE flat
-        # device buffer (mapfx.dist.ChunkLayout), so a host mirror of all of it is a
-        # single copy (the drop-in env pulls a step's results with one sync).
+        # device buffer, so a host mirror of all of it is a single copy (the drop-in env
+        # pulls a step's results with one sync)
         spec = {"pos": ((self.E, self.N, 2), torch.int32), "done": ((self.E, self.N), torch.uint8),
                 "t": ((self.E,), torch.int32), "err": ((1,), torch.int32)}
         if track_steps:
             spec["steps"] = ((self.E, self.N), torch.int32)
         spec.update(self.out_spec(None))
-        self.packed = bool(packed)
-        if self.packed:
-            from .dist import ChunkLayout
-            self._layout = ChunkLayout(spec)
-            self._flat = self._layout.alloc(dev)
-            v = self._layout.views(self._flat)
-            self.pos, self.done, self.t, self.err = v["pos"], v["done"], v["t"], v["err"]
-            self.pos.copy_(self.init_pos)
-            self.steps = v.get("steps")
-            self.out = {k: v[k] for k in self.out_spec(None)}
-        else:
-            self._layout = self._flat = None
-            self.pos = self.init_pos.clone()
-            self.done = torch.zeros((self.E, self.N), dtype=torch.uint8, device=dev)
-            self.t = torch.zeros((self.E,), dtype=torch.int32, device=dev)
-            self.steps = torch.zeros((self.E, self.N), dtype=torch.int32, device=dev) \
-                if track_steps else None
-            self.out = self._alloc_out(None)
+        v = self._alloc_spec(spec, packed)
+        self.pos, self.done, self.t, self.err = v["pos"], v["done"], v["t"], v["err"]
+        self.pos.copy_(self.init_pos)
+        self.steps = v.get("steps")
+        self.out = {k: v[k] for k in self.out_spec(None)}
         self._out_cache = {}          # outputs selection -> Out struct over self.out
         self._traj_cache = {}         # (outputs, buffer pointers) -> Out struct
-        self._dev_index = self.device.index if self.device.index is not None \
-            else torch.cuda.current_device()
         self._act_shape = (self.E, self.N)
         self._state = _abi.State(pos=ptr(self.pos), goal=ptr(self.goal),
                                  init_pos=ptr(self.init_pos), done=ptr(self.done), t=ptr(self.t),
@@ -165,8 +118,7 @@ class MapfGridBatch:
         return o
 
     def _alloc_out(self, T):
-        return {k: torch.zeros(shape, dtype=dt, device=self.device)
-                for k, (shape, dt) in self.out_spec(T).items()}
+        return self._zeros_of(self.out_spec(T))
 
     def _own_out(self, keys):
         """Cached Out struct over the persistent self.out buffers."""
@@ -175,13 +127,6 @@ class MapfGridBatch:
         if s is None:
             s = self._out_cache[k] = self._out_struct(self.out, keys=k)
         return s
-
-    def _call(self, fn, *args):
-        """Run a C-ABI call with self.device current (no context switch when it already is)."""
-        if torch.cuda.current_device() == self._dev_index:
-            return fn(*args, torch.cuda.current_stream().cuda_stream)
-        with torch.cuda.device(self.device):
-            return fn(*args, torch.cuda.current_stream().cuda_stream)
 
     def _out_struct(self, o, keys=None):
         s = _abi.Out()
@@ -195,12 +140,6 @@ class MapfGridBatch:
         s.err = ptr(self.err)
         return s
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            lib.mapfx_destroy(h)
-            self._h = None
-
     def info(self):
         inf = _abi.Info()
         check(lib.mapfx_query(self._h, ctypes.byref(inf)), "mapfx_query")
@@ -210,9 +149,7 @@ class MapfGridBatch:
     def reset(self, env_mask=None):
         """envs/mapf_gridworld.py:70-83 for the masked envs (all if None);
         refreshes obs/avail/term of every env.  Returns self.out."""
-        m = None
-        if env_mask is not None:
-            m = torch.as_tensor(env_mask, device=self.device).to(torch.uint8).contiguous()
+        m = _env_mask(env_mask, self.E, self.device)
         o = self._own_out(_OBS_KEYS)
         check(self._call(lib.mapfx_reset, self._h, ctypes.byref(self._state), ptr(m),
                          ctypes.byref(o)), "mapfx_reset")
@@ -227,19 +164,10 @@ class MapfGridBatch:
     def step(self, actions, outputs=None):
         """One env step of all E envs.  actions: [E, N] int8/int32/int64 tensor.
         `outputs` optionally restricts which outputs are written (names of self.out)."""
-        a = actions
-        if not (isinstance(a, torch.Tensor) and a.device == self.device and a.dtype in _DTYPES
-                and a.is_contiguous()):
-            a = torch.as_tensor(a, device=self.device)
-            if a.dtype not in _DTYPES:
-                a = a.to(torch.int64)
-            a = a.contiguous()
-        if a.shape != self._act_shape:
-            raise AssertionError("actions must be [%d, %d], got %s" % (self.E, self.N,
-                                                                     tuple(a.shape)))
+        a, adt = as_actions(actions, self.device, self._act_shape)
         o = self._own_out(outputs)
-        check(self._call(lib.mapfx_step, self._h, ctypes.byref(self._state), a.data_ptr(),
-                         _DTYPES[a.dtype], ctypes.byref(o)), "mapfx_step")
+        check(self._call(lib.mapfx_step, self._h, ctypes.byref(self._state), a.data_ptr(), adt,
+                         ctypes.byref(o)), "mapfx_step")
         return self.out
 
     def _traj_struct(self, traj, outputs):
@@ -261,13 +189,8 @@ class MapfGridBatch:
     def _rollout_actions(self, T, actions):
         if actions is None:
             return None, None, MAPFX_I8
-        a = torch.as_tensor(actions, device=self.device)
-        if a.dtype not in _DTYPES:
-            a = a.to(torch.int64)
-        a = a.contiguous()
-        if tuple(a.shape) != (T, self.E, self.N):
-            raise AssertionError("actions must be [T, E, N]")
-        return a, ptr(a), _DTYPES[a.dtype]
+        a, adt = as_actions(actions, self.device, (int(T), self.E, self.N))
+        return a, ptr(a), adt
 
     def rollout(self, T, actions=None, seed=0, t0=0, autoreset=False, traj=None, outputs=None):
         """T fused steps in one launch.  actions: [T, E, N] tensor or None (device
@@ -278,8 +201,8 @@ class MapfGridBatch:
         actions, ap, adt = self._rollout_actions(T, actions)
         o = self._traj_struct(traj, outputs)
         check(self._call(lib.mapfx_rollout, self._h, ctypes.byref(self._state), int(T), ap, adt,
-                         int(seed) & 0xFFFFFFFFFFFFFFFF, int(t0), 1 if autoreset else 0,
-                         ctypes.byref(o)), "mapfx_rollout")
+                         u64(seed), int(t0), 1 if autoreset else 0, ctypes.byref(o)),
+              "mapfx_rollout")
         return traj
 
     def rollout_plan(self, T, actions=None, seed=0, t0=0, autoreset=False, traj=None,
@@ -291,8 +214,8 @@ class MapfGridBatch:
         if traj is None:
             traj = self._alloc_out(T)
         actions, ap, adt = self._rollout_actions(T, actions)
-        return RolloutPlan(self, int(T), actions, ap, adt, int(seed) & 0xFFFFFFFFFFFFFFFF,
-                           int(t0), 1 if autoreset else 0, traj,
+        return RolloutPlan(self, int(T), actions, ap, adt, u64(seed), int(t0),
+                           1 if autoreset else 0, traj,
                            self._out_struct(traj, keys=None if outputs is None else tuple(outputs)),
                            stream if stream is not None else torch.cuda.current_stream(self.device),
                            events)
@@ -300,9 +223,8 @@ class MapfGridBatch:
     def gen_actions(self, T, seed, t0=0, out=None):
         if out is None:
             out = torch.empty((T, self.E, self.N), dtype=torch.int8, device=self.device)
-        with torch.cuda.device(self.device):
-            check(lib.mapfx_gen_actions(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(t0), int(T),
-                                        ptr(out), _stream_handle()), "mapfx_gen_actions")
+        check(self._call(lib.mapfx_gen_actions, self._h, u64(seed), int(t0), int(T), ptr(out)),
+              "mapfx_gen_actions")
         return out
 
     def pack_compact(self, traj_pos, traj_done, cell, done_bits):
@@ -347,34 +269,10 @@ class MapfGridBatch:
         if t is not None:
             self.t.copy_(torch.as_tensor(t, device=self.device).reshape(self.E))
 
-    def host_mirror(self):
-        """Pinned host copy of the packed buffer and its typed views (packed=True)."""
-        if not self.packed:
-            raise RuntimeError("host_mirror needs MapfGridBatch(..., packed=True)")
-        flat = torch.empty(self._layout.nbytes, dtype=torch.uint8, pin_memory=True)
-        return flat, self._layout.views(flat)
-
-    def pull(self, host_flat):
-        """Copy state + outputs into `host_flat` (host_mirror) and wait for it: the
-        one synchronisation of a drop-in step."""
-        host_flat.copy_(self._flat, non_blocking=True)
-        torch.cuda.current_stream(self.device).synchronize()
-        return host_flat
-
-    def check_err(self):
-        """Raise AssertionError like the reference (:91-92) if an env got an
-        action outside 0..4 since the last call (synchronises)."""
-        e = int(self.err.item())
-        if e:
-            self.err.zero_()
-            raise AssertionError("invalid action for env %d (actions must be in 0..4)" % (e - 1))
-
     # --------------------------------------------------- PyMARL-shaped views
     def avail_actions(self, avail=None):
         """[E, N, 5] int64 0/1, the layout of get_avail_actions (:198-224)."""
-        m = self.out["avail"] if avail is None else avail
-        bits = torch.arange(5, device=m.device, dtype=torch.uint8)
-        return ((m.unsqueeze(-1) >> bits) & 1).to(torch.int64)
+        return avail_bits(self.out["avail"] if avail is None else avail)
 
     def full_obs(self):
         """[E, N, H*W] view: every agent observes the same occupancy map (:161-183)."""

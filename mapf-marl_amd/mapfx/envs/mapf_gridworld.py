@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from ..batch import MapfGridBatch
-from ..maps import load_map, parse_scen_lines
+from ..maps import draw_scen, load_map
 from .multiagentenv import MultiAgentEnv
 
 ACTION_MEANING = {0: "LEFT", 1: "RIGHT", 2: "UP", 3: "DOWN", 4: "STAY"}  # :483-489
@@ -73,14 +73,10 @@ class MAPF_GRID(MultiAgentEnv):
 
     def __setup_agent(self):
         """:430-449 — same draws: random.randint(1, 25) then random.sample."""
-        random_scen_path = self._agent_path + str(random.randint(1, 25)) + ".scen"
-        assert os.path.exists(random_scen_path)
-        with open(random_scen_path, "r") as f:
-            f_lines = [row.rstrip() for row in f.readlines()][1:]
-        sampled_lines = random.sample(f_lines, self._n_agents)
-        for a_index, (start, goal) in enumerate(parse_scen_lines(sampled_lines)):
-            self._agent_init_pos[a_index] = start    # scen (x, y) used as (row, col)
-            self._agent_goal_pos[a_index] = goal
+        rows = draw_scen(random, self._agent_path, self._n_agents, more_than_n=False)
+        for a_index, (sx, sy, gx, gy) in enumerate(rows):
+            self._agent_init_pos[a_index] = (sx, sy)    # scen (x, y) used as (row, col)
+            self._agent_goal_pos[a_index] = (gx, gy)
         self.agent_starts = [self._agent_init_pos[i] for i in range(self._n_agents)]
         self.agent_goals = [self._agent_goal_pos[i] for i in range(self._n_agents)]
 

@@ -16,7 +16,7 @@ import random
 import numpy as np
 import torch
 
-from ..maps import load_map
+from ..maps import draw_scen, load_map
 from ..partial import MarlPartialBatch
 from .multiagentenv import MultiAgentEnv
 
@@ -78,18 +78,10 @@ class MARL_PARTIAL_ENV(MultiAgentEnv):
     def __setup_agent(self):
         """:896-920: same draws (random.randint(1, 25), random.sample), scen
         fields 4..7 = start x(col), start y(row), goal x, goal y."""
-        random_scen_path = self._agent_path + str(random.randint(1, 25)) + '.scen'
-        assert os.path.exists(random_scen_path)
-        with open(random_scen_path, "r") as f:
-            f_lines = [row.rstrip() for row in f.readlines()][1:]
-            assert len(f_lines) > self._n_agents
-            rand_lines = random.sample(f_lines, self._n_agents)
-            for a_index, f_line in enumerate(rand_lines):
-                line_list = f_line.replace('\t', ',').split(",")
-                s_col, s_row, f_col, f_row = (int(line_list[4]), int(line_list[5]),
-                                              int(line_list[6]), int(line_list[7]))
-                self._agent_init_pos[a_index] = (s_row, s_col)
-                self._agent_goal_pos[a_index] = (f_row, f_col)
+        rows = draw_scen(random, self._agent_path, self._n_agents)
+        for a_index, (s_col, s_row, f_col, f_row) in enumerate(rows):
+            self._agent_init_pos[a_index] = (s_row, s_col)
+            self._agent_goal_pos[a_index] = (f_row, f_col)
 
     def _load_instance(self):
         init = np.array([self._agent_init_pos], dtype=np.int32)

@@ -14,6 +14,7 @@
 from __future__ import annotations
 
 import io
+import os
 
 import numpy as np
 
@@ -58,11 +59,36 @@ def load_map(path: str) -> np.ndarray:
 def parse_scen_lines(lines):
     """Scenario lines -> list of ((sx, sy), (gx, gy)) as the reference reads them
     (envs/mapf_gridworld.py:442-445: `f_line.replace('\\t', ',').split(',')`)."""
+    return [((sx, sy), (gx, gy)) for sx, sy, gx, gy in scen_fields(lines)]
+
+
+def scen_fields(lines):
+    """Scenario lines -> [(start x, start y, goal x, goal y)] ints: fields 4..7 of the
+    reference's split.  MAPF_GRID uses (x, y) as (row, col) (quirk 2); marl_partial reads
+    them as (col, row) (:922-926)."""
     out = []
-    for f_line in lines:
-        parts = f_line.replace("\t", ",").split(",")
-        out.append(((int(parts[4]), int(parts[5])), (int(parts[6]), int(parts[7]))))
+    for line in lines:
+        v = line.replace("\t", ",").split(",")
+        out.append((int(v[4]), int(v[5]), int(v[6]), int(v[7])))
     return out
+
+
+def read_scen(path):
+    """The lines of a MovingAI .scen file as the reference reads them: rstrip()ed, the
+    header line dropped.  A missing file is an AssertionError (the reference asserts)."""
+    assert os.path.exists(path), "scenario file %s does not exist" % path
+    with open(path) as f:
+        return [row.rstrip() for row in f.readlines()][1:]
+
+
+def draw_scen(rng, agents_path, n, more_than_n=True, read=read_scen):
+    """The reference envs' scenario draw from `rng` (the `random` module or a
+    random.Random): rng.randint(1, 25) names the file agents_path + "<k>.scen", rng.sample
+    picks n of its lines -> their scen_fields.  more_than_n: the file must hold more than
+    n lines (marl_partial.py:913; MAPF_GRID has no such assert)."""
+    lines = read(agents_path + str(rng.randint(1, 25)) + ".scen")
+    assert not more_than_n or len(lines) > n
+    return scen_fields(rng.sample(lines, n))
 
 
 SCEN_LMAX = 4096  # mapfx_partial_draw sorts at most this many line keys per env
@@ -78,17 +104,13 @@ def load_scen_table(agents_path: str, H: int, W: int, n_files: int = 25):
     and rows past a file's length zero.  A missing file is an AssertionError (the reference
     asserts it exists); the kernel trusts the table, so a coordinate outside [0, H) x [0, W)
     and Lmax > 4096 are ValueErrors here."""
-    import os
     files = []
     for k in range(1, int(n_files) + 1):
         path = agents_path + str(k) + ".scen"
-        assert os.path.exists(path), "scenario file %s does not exist" % path
-        with open(path) as f:
-            rows = [row.rstrip() for row in f.readlines()][1:]
+        rows = scen_fields(read_scen(path))
         tab = np.zeros((len(rows), 4), dtype=np.int64)
-        for j, row in enumerate(rows):
-            v = row.replace("\t", ",").split(",")
-            tab[j] = (int(v[5]), int(v[4]), int(v[7]), int(v[6]))
+        for j, (sx, sy, gx, gy) in enumerate(rows):
+            tab[j] = (sy, sx, gy, gx)
             r, c = tab[j, 0::2], tab[j, 1::2]
             if r.min() < 0 or r.max() >= H or c.min() < 0 or c.max() >= W:
                 raise ValueError("%s line %d: (row, col) %s / %s outside the %d x %d grid"

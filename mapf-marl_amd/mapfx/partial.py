@@ -15,10 +15,9 @@ import numpy as np
 import torch
 
 from . import _abi
-from ._abi import MAPFX_I8, MAPFX_I32, MAPFX_I64, check, lib, ptr
-from .maps import map_stride, pack_bits
-
-_DTYPES = {torch.int8: MAPFX_I8, torch.int32: MAPFX_I32, torch.int64: MAPFX_I64}
+from ._abi import MAPFX_I8, check, lib, ptr
+from ._base import DeviceBatch, as_actions, avail_bits, parse_agents, parse_map, u64
+from ._base import env_mask as _env_mask    # (the methods' own `env_mask` argument hides it)
 
 DEFAULTS = dict(  # MARL_PARTIAL_ENV.__init__ defaults (:25-47)
     obs_window=5, obs_knn_agents=5, episode_limit=100, move_reward=-0.01, stay_reward=-0.02,
@@ -26,7 +25,7 @@ DEFAULTS = dict(  # MARL_PARTIAL_ENV.__init__ defaults (:25-47)
     complete_reward=1000, complete_fac=1.5, gamma=0.99)
 
 
-class MarlPartialBatch:
+class MarlPartialBatch(DeviceBatch):
     """E independent MARL_PARTIAL_ENV envs on one GPU.  `grids` [E|1, H, W]
     (nonzero = obstacle) or `bits` [E|1, map_stride]; init_pos / goals [E, N, 2]."""
 
@@ -38,28 +37,9 @@ class MarlPartialBatch:
         p = dict(DEFAULTS)
         p.update(params)
         self.params = p
-        self.device = torch.device(device if device is not None else "cuda")
-        if self.device.type != "cuda":
-            raise RuntimeError("MarlPartialBatch runs on a HIP device only (got %s)" % self.device)
-        init_pos = np.array(init_pos, dtype=np.int32)
-        goals = np.array(goals, dtype=np.int32)
-        if init_pos.ndim != 3 or init_pos.shape[-1] != 2 or goals.shape != init_pos.shape:
-            raise ValueError("init_pos/goals must both be [E, N, 2]")
-        self.E, self.N = int(init_pos.shape[0]), int(init_pos.shape[1])
-        if bits is None:
-            g = np.asarray(grids)
-            if g.ndim == 2:
-                g = g[None]
-            self.H, self.W = int(g.shape[1]), int(g.shape[2])
-            bits = pack_bits(g)
-        else:
-            self.H, self.W = hw
-        bits = np.array(bits, dtype=np.uint8)
-        if bits.ndim == 1:
-            bits = bits[None]
-        if bits.shape[1] != map_stride(self.H, self.W) or bits.shape[0] not in (1, self.E):
-            raise ValueError("bits must be [E or 1, %d]" % map_stride(self.H, self.W))
-        self.map_shared = bits.shape[0] == 1 and self.E != 1
+        super().__init__(device)
+        self.E, self.N, init_pos, goals = parse_agents(init_pos, goals, "init_pos/goals")
+        self.H, self.W, bits, self.map_shared = parse_map(grids, bits, hw, self.E)
         self.episode_limit = int(p["episode_limit"])
         cfg = _abi.PCfg(H=self.H, W=self.W, n_agents=self.N, n_envs=self.E,
                         env_offset=int(env_offset), episode_limit=self.episode_limit,
@@ -72,16 +52,9 @@ class MarlPartialBatch:
                         env_collide_reward=float(p["env_collide_reward"]),
                         complete_reward=float(p["complete_reward"]),
                         complete_fac=float(p["complete_fac"]), gamma=float(p["gamma"]))
-        with torch.cuda.device(self.device):
-            h = ctypes.c_void_p()
-            check(lib.mapfx_partial_create(ctypes.byref(cfg), ctypes.byref(h)),
-                  "mapfx_partial_create")
-        self._h = h
-        self._dev_index = self.device.index if self.device.index is not None \
-            else torch.cuda.current_device()
-        self.obs_dim = int(lib.mapfx_partial_obs_dim(h))
-        E, N, dev = self.E, self.N, self.device
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+        self._create(lib.mapfx_partial_create, lib.mapfx_partial_destroy, cfg)
+        self.obs_dim = int(lib.mapfx_partial_obs_dim(self._h))
+        E, N, dev, z = self.E, self.N, self.device, self._zeros
         self.bits = torch.as_tensor(bits).to(dev)
         self.init_pos = torch.as_tensor(init_pos).to(dev).contiguous()
         self.goal = torch.as_tensor(goals).to(dev).contiguous()
@@ -92,15 +65,7 @@ class MarlPartialBatch:
                 "err": ((1,), torch.int32), "reward": ((E,), torch.float64),
                 "obs": ((E, N, self.obs_dim), torch.float32), "state": ((E, 3), torch.float32),
                 "avail": ((E, N), torch.uint8)}
-        self.packed = bool(packed)
-        if self.packed:
-            from .dist import ChunkLayout
-            self._layout = ChunkLayout(spec)
-            self._flat = self._layout.alloc(dev)
-            v = self._layout.views(self._flat)
-        else:
-            self._layout = self._flat = None
-            v = {k: z(shape, dt) for k, (shape, dt) in spec.items()}
+        v = self._alloc_spec(spec, packed)
         self.pos, self.done, self.terminated, self.t, self.err = (
             v["pos"], v["done"], v["terminated"], v["t"], v["err"])
         self.pos.copy_(self.init_pos)
@@ -135,26 +100,13 @@ class MarlPartialBatch:
                                   state=ptr(self.out["state"]), avail=ptr(self.out["avail"]),
                                   err=ptr(self.err))
         self._scen = None   # set_scenarios: the device scenario draw's table and counters
+        self._traj_cache = {}   # rollout: (T, obs, policy mode) -> its trajectory tensors
         self.compute_goal_dist()
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            lib.mapfx_partial_destroy(h)
-            self._h = None
-
-    def _call(self, fn, *args):
-        """Run a C-ABI call with self.device current (no context switch when it already is)."""
-        if torch.cuda.current_device() == self._dev_index:
-            return fn(*args, torch.cuda.current_stream().cuda_stream)
-        with torch.cuda.device(self.device):
-            return fn(*args, torch.cuda.current_stream().cuda_stream)
 
     # ------------------------------------------------------------------ API
     def compute_goal_dist(self, env_mask=None):
         """BFS tables of the (masked) envs' goals (:906-928)."""
-        m = None if env_mask is None else \
-            torch.as_tensor(env_mask, device=self.device).to(torch.uint8).contiguous()
+        m = _env_mask(env_mask, self.E, self.device)
         check(self._call(lib.mapfx_partial_goal_dist, self._h, ctypes.byref(self._state), ptr(m)),
               "mapfx_partial_goal_dist")
 
@@ -186,7 +138,7 @@ class MarlPartialBatch:
         self.episode = torch.zeros((self.E,), dtype=torch.int32, device=self.device)
         # the draw's own report (1 + a bad env), apart from the invalid-action one
         self.scen_err = torch.zeros((1,), dtype=torch.int32, device=self.device)
-        self._scen = _abi.PScen(seed=int(seed) & 0xFFFFFFFFFFFFFFFF, lines=ptr(self.scen_lines),
+        self._scen = _abi.PScen(seed=u64(seed), lines=ptr(self.scen_lines),
                                 n_lines=ptr(self.scen_n_lines), n_files=int(lines.shape[0]),
                                 l_max=int(lines.shape[1]), init_pos=ptr(self.init_pos),
                                 goal=ptr(self.goal), episode=ptr(self.episode), mask=None,
@@ -199,8 +151,7 @@ class MarlPartialBatch:
         of instances; a file with no more than n_agents lines shows in check_err()."""
         if self._scen is None:
             raise RuntimeError("redraw needs set_scenarios(lines, n_lines, seed) first")
-        m = None if env_mask is None else \
-            torch.as_tensor(env_mask, device=self.device).to(torch.uint8).contiguous()
+        m = _env_mask(env_mask, self.E, self.device)
         self._scen.mask = ptr(m)
         check(self._call(lib.mapfx_partial_draw, self._h, ctypes.byref(self._scen)),
               "mapfx_partial_draw")
@@ -208,8 +159,7 @@ class MarlPartialBatch:
 
     def reset(self, env_mask=None):
         """:125-163 for the masked envs (all if None); observations of every env."""
-        m = None if env_mask is None else \
-            torch.as_tensor(env_mask, device=self.device).to(torch.uint8).contiguous()
+        m = _env_mask(env_mask, self.E, self.device)
         check(self._call(lib.mapfx_partial_reset, self._h, ctypes.byref(self._state), ptr(m),
                          ctypes.byref(self._obs_out)), "mapfx_partial_reset")
         return self.out
@@ -221,14 +171,9 @@ class MarlPartialBatch:
 
     def step(self, actions):
         """One step of all E envs (:165-310).  actions: [E, N] int8/int32/int64."""
-        a = torch.as_tensor(actions, device=self.device)
-        if a.dtype not in _DTYPES:
-            a = a.to(torch.int64)
-        a = a.contiguous()
-        if tuple(a.shape) != (self.E, self.N):
-            raise AssertionError("actions must be [%d, %d]" % (self.E, self.N))
-        check(self._call(lib.mapfx_partial_step, self._h, ctypes.byref(self._state), ptr(a),
-                         _DTYPES[a.dtype], ctypes.byref(self._out)), "mapfx_partial_step")
+        a, dt = as_actions(actions, self.device, (self.E, self.N))
+        check(self._call(lib.mapfx_partial_step, self._h, ctypes.byref(self._state), a.data_ptr(),
+                         dt, ctypes.byref(self._out)), "mapfx_partial_step")
         return self.out
 
     TRAJ_KEYS = ("reward", "obs", "state", "avail", "pos", "terminated", "actions")
@@ -277,24 +222,19 @@ class MarlPartialBatch:
             if not 0 <= eps_q <= 2 ** 32:
                 raise ValueError("eps_q must be in 0..2**32")
             a, dt = None, MAPFX_I8
-            pol = _abi.PPolicy(seed=int(seed) & 0xFFFFFFFFFFFFFFFF, eps_q=eps_q, t0=int(t0))
+            pol = _abi.PPolicy(seed=u64(seed), eps_q=eps_q, t0=int(t0))
         else:
-            a = torch.as_tensor(actions, device=self.device)
-            if a.dtype not in _DTYPES:
-                a = a.to(torch.int64)
-            a = a.contiguous()
+            a, dt = as_actions(actions, self.device)   # [T, E, N] with T its own: checked here
             if a.dim() != 3 or tuple(a.shape[1:]) != (self.E, self.N) or \
                     (T is not None and int(T) != a.shape[0]):
                 raise AssertionError("actions must be [T, %d, %d]" % (self.E, self.N))
-            T, dt, pol = int(a.shape[0]), _DTYPES[a.dtype], None
+            T, pol = int(a.shape[0]), None
         spec = self._traj_spec(T, obs, policy)
         if out is None:
-            cache = self.__dict__.setdefault("_traj_cache", {})
             key = (T, bool(obs), policy)
-            if key not in cache:
-                cache[key] = {k: torch.zeros(shape, dtype=d, device=self.device)
-                              for k, (shape, d) in spec.items()}
-            out = cache[key]
+            out = self._traj_cache.get(key)
+            if out is None:
+                out = self._traj_cache[key] = self._zeros_of(spec)
         else:
             for k, t in out.items():
                 if k not in spec:
@@ -310,32 +250,13 @@ class MarlPartialBatch:
                          ctypes.byref(traj)), "mapfx_partial_rollout")
         return out
 
-    def host_mirror(self):
-        """Pinned host copy of the packed buffer and its typed views (packed=True)."""
-        if not self.packed:
-            raise RuntimeError("host_mirror needs MarlPartialBatch(..., packed=True)")
-        flat = torch.empty(self._layout.nbytes, dtype=torch.uint8, pin_memory=True)
-        return flat, self._layout.views(flat)
-
-    def pull(self, host_flat):
-        """Copy the packed buffer into `host_flat` and wait for it (one sync)."""
-        host_flat.copy_(self._flat, non_blocking=True)
-        torch.cuda.current_stream(self.device).synchronize()
-        return host_flat
-
     def check_err(self):
-        if self._scen is not None:
-            e = int(self.scen_err.item())
-            if e:
-                self.scen_err.zero_()
-                raise AssertionError("scenario file with no more than n_agents lines drawn for "
-                                     "env %d" % (e - 1))
-        e = int(self.err.item())
+        e = self._take_err(self.scen_err) if self._scen is not None else 0
         if e:
-            self.err.zero_()
-            raise AssertionError("invalid action for env %d (actions must be in 0..4)" % (e - 1))
+            raise AssertionError("scenario file with no more than n_agents lines drawn for "
+                                 "env %d" % (e - 1))
+        super().check_err()
 
     def avail_actions(self):
         """[E, N, 5] int64 0/1 (get_avail_actions)."""
-        bits = torch.arange(5, device=self.device, dtype=torch.uint8)
-        return ((self.out["avail"].unsqueeze(-1) >> bits) & 1).to(torch.int64)
+        return avail_bits(self.out["avail"])

@@ -25,67 +25,70 @@ import torch
 
 from . import _abi
 from ._abi import check, lib, ptr
-from .maps import map_stride, pack_bits, primal_gen_luts, primal_world
+from ._base import DeviceBatch, check_on_grid, env_mask, parse_agents, parse_map, u64
+from .maps import map_stride, primal_gen_luts, primal_world
 
 _OUT_KEYS = ("reward", "done", "next_mask", "on_goal", "valid", "obs", "vec")
 
 
-class PrimalBatch:
+def _check_placement(starts, goals, bits, H, W):
+    """Distinct in-bounds starts and goals on free cells: PRIMAL keeps agents,
+    goals and obstacles in one array per kind (:44-66), so the kernel assumes it."""
+    for arr, what in ((starts, "starts"), (goals, "goals")):
+        check_on_grid(arr, H, W, what)
+        flat = arr[..., 0].astype(np.int64) * W + arr[..., 1]
+        if any(len(np.unique(row)) != arr.shape[1] for row in flat):
+            raise ValueError("%s must be distinct within a world" % what)
+    cells = starts[..., 0].astype(np.int64) * W + starts[..., 1]
+    b = bits if bits.shape[0] == cells.shape[0] else np.repeat(bits, cells.shape[0], 0)
+    blocked = (np.take_along_axis(b, cells >> 3, 1) >> (cells & 7)) & 1
+    if blocked.any():
+        raise ValueError("an agent starts on an obstacle")
+
+
+class PrimalBatch(DeviceBatch):
     """E PRIMAL worlds on one GPU.  `grids` [E|1, H, W] (negative = obstacle, as
     PRIMAL's world0) or `bits` [E|1, map_stride]; starts / goals [E, N, 2] (row, col)."""
 
     def __init__(self, starts, goals, grids=None, bits=None, hw=None, observation_size=10,
                  device=None, diagonal=False, past=None, blocking=False):
+        super().__init__(device)
+        E, N, starts, goals = parse_agents(starts, goals, "starts/goals")
+        H, W, bits, map_shared = parse_map(grids, bits, hw, E, obstacle=lambda g: g < 0)
+        _check_placement(starts, goals, bits, H, W)
+        if diagonal:
+            # agents_past (DIAGONAL_MOVEMENT): equal to the starts in a fresh world (:55-66).
+            # The kernels read past as int2 at [e * N + i] and primal_seq_kernel packs it
+            # as biased u8 (row, col) bytes: shape and bounds are checked here
+            past = starts if past is None else np.array(past, dtype=np.int32)
+            if past.shape != starts.shape:
+                raise ValueError("past must be [E, N, 2] like the starts, got %s" % (past.shape,))
+            check_on_grid(past, H, W, "past")
+        self._init(E, N, H, W, map_shared, observation_size, diagonal, blocking,
+                   (bits, starts, goals, past if diagonal else None))
+
+    def _init(self, E, N, H, W, map_shared, observation_size, diagonal, blocking, host=None):
+        """The handle and the device state: `host` = checked (bits, pos, goal, past) arrays
+        (__init__), or None: zeroed on the device for the generator to fill (random; no copy,
+        so no host synchronisation)."""
         self.blocking = bool(blocking)
-        self.device = torch.device(device if device is not None else "cuda")
-        if self.device.type != "cuda":
-            raise RuntimeError("PrimalBatch runs on a HIP device only (got %s)" % self.device)
-        starts = np.array(starts, dtype=np.int32)
-        goals = np.array(goals, dtype=np.int32)
-        if starts.ndim != 3 or starts.shape[-1] != 2 or goals.shape != starts.shape:
-            raise ValueError("starts/goals must both be [E, N, 2]")
-        self.E, self.N = int(starts.shape[0]), int(starts.shape[1])
-        if bits is None:
-            g = np.asarray(grids)
-            if g.ndim == 2:
-                g = g[None]
-            self.H, self.W = int(g.shape[1]), int(g.shape[2])
-            bits = pack_bits(g < 0)
-        else:
-            self.H, self.W = hw
-        bits = np.array(bits, dtype=np.uint8)
-        if bits.ndim == 1:
-            bits = bits[None]
-        if bits.shape[1] != map_stride(self.H, self.W) or bits.shape[0] not in (1, self.E):
-            raise ValueError("bits must be [E or 1, %d]" % map_stride(self.H, self.W))
-        self._check_placement(starts, goals, bits)
-        self.map_shared = bits.shape[0] == 1 and self.E != 1
+        self.E, self.N, self.H, self.W, self.map_shared = E, N, H, W, map_shared
         self.s = int(observation_size)
         self.diagonal = bool(diagonal)
         self.n_actions = 9 if self.diagonal else 5
-        cfg = _abi.QCfg(H=self.H, W=self.W, n_agents=self.N, n_envs=self.E, obs_size=self.s,
-                        map_shared=1 if self.map_shared else 0, diagonal=1 if self.diagonal else 0)
-        with torch.cuda.device(self.device):
-            h = ctypes.c_void_p()
-            check(lib.mapfx_primal_create(ctypes.byref(cfg), ctypes.byref(h)), "mapfx_primal_create")
-        self._h = h
-        dev = self.device
-        self.bits = torch.as_tensor(bits).to(dev)
-        self.pos = torch.as_tensor(starts).to(dev).contiguous()
-        self.goal = torch.as_tensor(goals).to(dev).contiguous()
-        self.err = torch.zeros((1,), dtype=torch.int32, device=dev)
-        # agents_past (DIAGONAL_MOVEMENT): equal to the starts in a fresh world (:55-66)
-        self.past = None
-        if self.diagonal:
-            pp = starts if past is None else np.array(past, dtype=np.int32)
-            # the kernels read past as int2 at [e * N + i] and primal_seq_kernel packs it
-            # as biased u8 (row, col) bytes: shape and bounds are checked here
-            if pp.shape != starts.shape:
-                raise ValueError("past must be [E, N, 2] like the starts, got %s" % (pp.shape,))
-            if pp.size and ((pp[..., 0] < 0).any() or (pp[..., 0] >= self.H).any()
-                            or (pp[..., 1] < 0).any() or (pp[..., 1] >= self.W).any()):
-                raise ValueError("past outside the %dx%d grid" % (self.H, self.W))
-            self.past = torch.as_tensor(pp).to(dev).contiguous()
+        cfg = _abi.QCfg(H=H, W=W, n_agents=N, n_envs=E, obs_size=self.s,
+                        map_shared=1 if map_shared else 0, diagonal=1 if self.diagonal else 0)
+        self._create(lib.mapfx_primal_create, lib.mapfx_primal_destroy, cfg)
+        if host is None:
+            z = self._zeros
+            self.bits = z((E, map_stride(H, W)), torch.uint8)
+            self.pos, self.goal = z((E, N, 2), torch.int32), z((E, N, 2), torch.int32)
+            self.past = z((E, N, 2), torch.int32) if self.diagonal else None
+        else:
+            self.bits, self.pos, self.goal, self.past = (
+                None if a is None else torch.as_tensor(a).to(self.device).contiguous()
+                for a in host)
+        self.err = self._zeros((1,), torch.int32)
         self._state = _abi.QState(pos=ptr(self.pos), goal=ptr(self.goal), map_bits=ptr(self.bits),
                                   past=ptr(self.past))
         self._K = -1
@@ -94,7 +97,7 @@ class PrimalBatch:
         self.obs_out = None
         # the device generator (regenerate): episode counters, and no tables until
         # set_generator / PrimalBatch.random names the seed and the distribution
-        self.episode = torch.zeros((self.E,), dtype=torch.int32, device=dev)
+        self.episode = self._zeros((self.E,), torch.int32)
         self.gen_seed, self.env_offset = 0, 0
         self.side_lut = self.prob_lut = None
         self._generated = False
@@ -110,37 +113,9 @@ class PrimalBatch:
         region.  World e is a function of (seed, env_offset + e, its episode counter)
         alone.  Nothing of the generated state is read back or checked on the host."""
         self = cls.__new__(cls)
-        self.blocking = bool(blocking)
-        self.device = torch.device(device if device is not None else "cuda")
-        if self.device.type != "cuda":
-            raise RuntimeError("PrimalBatch runs on a HIP device only (got %s)" % self.device)
-        self.E, self.N = int(E), int(N)
-        self.H, self.W = int(hw[0]), int(hw[1])
-        self.map_shared = False
-        self.s = int(observation_size)
-        self.diagonal = bool(diagonal)
-        self.n_actions = 9 if self.diagonal else 5
-        cfg = _abi.QCfg(H=self.H, W=self.W, n_agents=self.N, n_envs=self.E, obs_size=self.s,
-                        map_shared=0, diagonal=1 if self.diagonal else 0)
-        with torch.cuda.device(self.device):
-            h = ctypes.c_void_p()
-            check(lib.mapfx_primal_create(ctypes.byref(cfg), ctypes.byref(h)), "mapfx_primal_create")
-        self._h = h
-        dev = self.device
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
-        self.bits = z((self.E, map_stride(self.H, self.W)), torch.uint8)
-        self.pos = z((self.E, self.N, 2), torch.int32)
-        self.goal = z((self.E, self.N, 2), torch.int32)
-        self.past = z((self.E, self.N, 2), torch.int32) if self.diagonal else None
-        self.err = z((1,), torch.int32)
-        self.episode = z((self.E,), torch.int32)
-        self._state = _abi.QState(pos=ptr(self.pos), goal=ptr(self.goal), map_bits=ptr(self.bits),
-                                  past=ptr(self.past))
-        self._K = -1
-        self.out = None
-        self._Q = -1
-        self.obs_out = None
-        self._generated = False
+        DeviceBatch.__init__(self, device)
+        self._init(int(E), int(N), int(hw[0]), int(hw[1]), False, observation_size, diagonal,
+                   blocking)
         self.set_generator(seed, SIZE=SIZE, PROB=PROB, env_offset=env_offset, luts=luts)
         self.regenerate()
         return self
@@ -151,7 +126,7 @@ class PrimalBatch:
         (side_lut, prob_lut) of power-of-two lengths.  Tables given on the host are
         checked here (every side in 1..min(H, W) with side^2 >= N: ValueError); device
         tensors are taken as they are, and a bad side is reported per world by check_err()."""
-        self.gen_seed, self.env_offset = int(seed) & 0xFFFFFFFFFFFFFFFF, int(env_offset)
+        self.gen_seed, self.env_offset = u64(seed), int(env_offset)
         side, prob = primal_gen_luts(SIZE, PROB) if luts is None else luts
         if not torch.is_tensor(side):
             side = np.asarray(side, dtype=np.int32).reshape(-1)
@@ -182,49 +157,18 @@ class PrimalBatch:
                 raise ValueError("a shared-map batch regenerates with keep_map=True only")
             if self.side_lut is None:
                 raise ValueError("no world distribution: call set_generator(seed, SIZE, PROB) first")
-        m = None
-        if mask is not None:
-            m = torch.as_tensor(mask, device=self.device)
-            if m.shape != (self.E,):
-                raise AssertionError("mask must be [%d]" % self.E)
-            m = (m if m.dtype == torch.uint8 else (m != 0).to(torch.uint8)).contiguous()
+        m = env_mask(mask, self.E, self.device)
         gen = _abi.QGen(seed=self.gen_seed, env_offset=self.env_offset,
                         side_lut=ptr(self.side_lut), n_side=0 if self.side_lut is None else self.side_lut.numel(),
                         prob_lut=ptr(self.prob_lut), n_prob=0 if self.prob_lut is None else self.prob_lut.numel(),
                         episode=ptr(self.episode), mask=ptr(m), map_bits=ptr(self.bits),
                         keep_map=1 if keep_map else 0, err=ptr(self.err))
-        with torch.cuda.device(self.device):
-            check(lib.mapfx_primal_generate(self._h, ctypes.byref(self._state), ctypes.byref(gen),
-                                            torch.cuda.current_stream().cuda_stream),
-                  "mapfx_primal_generate")
+        check(self._call(lib.mapfx_primal_generate, self._h, ctypes.byref(self._state),
+                         ctypes.byref(gen)), "mapfx_primal_generate")
         self._generated = True
 
-    def _check_placement(self, starts, goals, bits):
-        """Distinct in-bounds starts and goals on free cells: PRIMAL keeps agents,
-        goals and obstacles in one array per kind (:44-66), so the kernel assumes it."""
-        H, W = self.H, self.W
-        for arr, what in ((starts, "starts"), (goals, "goals")):
-            if (arr[..., 0] < 0).any() or (arr[..., 0] >= H).any() or (arr[..., 1] < 0).any() \
-                    or (arr[..., 1] >= W).any():
-                raise ValueError("%s out of bounds" % what)
-            flat = arr[..., 0].astype(np.int64) * W + arr[..., 1]
-            if any(len(np.unique(row)) != self.N for row in flat):
-                raise ValueError("%s must be distinct within a world" % what)
-        cells = starts[..., 0].astype(np.int64) * W + starts[..., 1]
-        b = bits if bits.shape[0] == cells.shape[0] else np.repeat(bits, cells.shape[0], 0)
-        blocked = (np.take_along_axis(b, cells >> 3, 1) >> (cells & 7)) & 1
-        if blocked.any():
-            raise ValueError("an agent starts on an obstacle")
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            lib.mapfx_primal_destroy(h)
-            self._h = None
-
     def _alloc(self, K):
-        E, s, dev = self.E, self.s, self.device
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+        E, s, z = self.E, self.s, self._zeros
         self.out = {"reward": z((E, K), torch.float64), "done": z((E, K), torch.uint8),
                     "next_mask": z((E, K), torch.int16 if self.diagonal else torch.uint8),
                     "on_goal": z((E, K), torch.uint8),
@@ -251,25 +195,18 @@ class PrimalBatch:
         K = int(ids.shape[1])
         if K != self._K:
             self._alloc(K)
-        with torch.cuda.device(self.device):
-            if events is None:
-                check(lib.mapfx_primal_act(self._h, ctypes.byref(self._state), ptr(ids), ptr(acts), K,
-                                           ctypes.byref(self._out),
-                                           torch.cuda.current_stream().cuda_stream),
-                      "mapfx_primal_act")
-            else:
-                check(lib.mapfx_primal_act_timed(self._h, ctypes.byref(self._state), ptr(ids), ptr(acts),
-                                                 K, ctypes.byref(self._out), events[0].cuda_event,
-                                                 events[1].cuda_event,
-                                                 torch.cuda.current_stream().cuda_stream),
-                      "mapfx_primal_act_timed")
-            if self.blocking:
-                o = self.out
-                check(lib.mapfx_primal_blocking(self._h, ctypes.byref(self._state), ptr(ids), ptr(acts), K,
-                                                ptr(o["valid"]), ptr(o["on_goal"]), ptr(o["reward"]),
-                                                ptr(o["blocking"]), ptr(o["n_blocking"]),
-                                                torch.cuda.current_stream().cuda_stream),
-                      "mapfx_primal_blocking")
+        args = (self._h, ctypes.byref(self._state), ptr(ids), ptr(acts), K)
+        if events is None:
+            check(self._call(lib.mapfx_primal_act, *args, ctypes.byref(self._out)),
+                  "mapfx_primal_act")
+        else:
+            check(self._call(lib.mapfx_primal_act_timed, *args, ctypes.byref(self._out),
+                             events[0].cuda_event, events[1].cuda_event), "mapfx_primal_act_timed")
+        if self.blocking:
+            o = self.out
+            check(self._call(lib.mapfx_primal_blocking, *args, ptr(o["valid"]), ptr(o["on_goal"]),
+                             ptr(o["reward"]), ptr(o["blocking"]), ptr(o["n_blocking"])),
+                  "mapfx_primal_blocking")
         return self.out
 
     def observe(self, agent_ids=None, prev_actions=None):
@@ -295,18 +232,14 @@ class PrimalBatch:
         if ids is None and Q != self.N:
             raise AssertionError("without agent_ids every agent is queried: Q must be %d" % self.N)
         if Q != self._Q:
-            E, s, dev = self.E, self.s, self.device
-            z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+            E, s, z = self.E, self.s, self._zeros
             self.obs_out = {"obs": z((E, Q, 4, s, s), torch.uint8), "vec": z((E, Q, 3), torch.float64),
                             "next_mask": z((E, Q), torch.int16 if self.diagonal else torch.uint8),
                             "on_goal": z((E, Q), torch.uint8), "done": z((E, Q), torch.uint8)}
             self._obs_out = _abi.QOut(err=ptr(self.err), **{k: ptr(v) for k, v in self.obs_out.items()})
             self._Q = Q
-        with torch.cuda.device(self.device):
-            check(lib.mapfx_primal_observe(self._h, ctypes.byref(self._state), ptr(ids), ptr(acts), Q,
-                                           ctypes.byref(self._obs_out),
-                                           torch.cuda.current_stream().cuda_stream),
-                  "mapfx_primal_observe")
+        check(self._call(lib.mapfx_primal_observe, self._h, ctypes.byref(self._state), ptr(ids),
+                         ptr(acts), Q, ctypes.byref(self._obs_out)), "mapfx_primal_observe")
         return self.obs_out
 
     def blocking_count(self, agent_ids):
@@ -315,17 +248,14 @@ class PrimalBatch:
         ids = torch.as_tensor(agent_ids, device=self.device).to(torch.int32).contiguous()
         if ids.shape != (self.E,):
             raise AssertionError("agent_ids must be [%d]" % self.E)
-        counts = torch.zeros((self.E,), dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            check(lib.mapfx_primal_blocking_count(self._h, ctypes.byref(self._state), ptr(ids),
-                                                  ptr(counts), torch.cuda.current_stream().cuda_stream),
-                  "mapfx_primal_blocking_count")
+        counts = self._zeros((self.E,), torch.int32)
+        check(self._call(lib.mapfx_primal_blocking_count, self._h, ctypes.byref(self._state),
+                         ptr(ids), ptr(counts)), "mapfx_primal_blocking_count")
         return counts
 
     def check_err(self):
-        e = int(self.err.item())
+        e = self._take_err(self.err)
         if e:
-            self.err.zero_()
             if self._generated:
                 raise AssertionError("invalid (agent_id, action), or a world the generator could not "
                                      "build (a side that does not fit, too few free cells), for world %d"

@@ -43,7 +43,6 @@ names), with no host loop and no copy of instances per reset.
 from __future__ import annotations
 
 import ctypes
-import os
 import random
 from functools import partial
 
@@ -51,11 +50,12 @@ import numpy as np
 import torch
 
 from . import _abi
-from ._abi import MAPFX_I8, MAPFX_I32, MAPFX_I64, check, lib, ptr
-from .maps import load_map, load_scen_table
+from ._abi import check, lib, ptr
+from ._base import DTYPES as _ADT    # noqa: F401  (tools/runner_host_probe.py replays `run` with it)
+from ._base import as_actions
+from .maps import draw_scen, load_map, load_scen_table, read_scen
 from .partial import MarlPartialBatch
 
-_ADT = {torch.int8: MAPFX_I8, torch.int32: MAPFX_I32, torch.int64: MAPFX_I64}
 _ROW_DTYPES = {"obs": torch.float32, "state": torch.float32, "avail_actions": torch.int32,
                "actions": torch.int64, "actions_onehot": torch.float32, "reward": torch.float32,
                "terminated": torch.uint8, "filled": torch.int64}
@@ -71,22 +71,14 @@ _SCEN_CACHE = {}
 def _scen_lines(path):
     lines = _SCEN_CACHE.get(path)
     if lines is None:
-        assert os.path.exists(path)
-        with open(path) as f:
-            lines = _SCEN_CACHE[path] = [row.rstrip() for row in f.readlines()][1:]
+        lines = _SCEN_CACHE[path] = read_scen(path)
     return lines
 
 
 def _scen_draw(rng, agents_path, n):
     """:896-920 with an explicit Random: (starts, goals) as (row, col)."""
-    lines = _scen_lines(agents_path + str(rng.randint(1, 25)) + ".scen")
-    assert len(lines) > n
-    starts, goals = [], []
-    for line in rng.sample(lines, n):
-        v = line.replace("\t", ",").split(",")
-        starts.append((int(v[5]), int(v[4])))
-        goals.append((int(v[7]), int(v[6])))
-    return starts, goals
+    rows = draw_scen(rng, agents_path, n, read=_scen_lines)
+    return [(sy, sx) for sx, sy, _, _ in rows], [(gy, gx) for _, _, gx, gy in rows]
 
 
 class ParallelRunner:
@@ -136,8 +128,7 @@ class ParallelRunner:
         self.env_info = {"state_shape": 3, "obs_shape": self.env.obs_dim, "n_actions": 5,
                          "n_agents": self.n_agents, "episode_limit": self.env.episode_limit}
         self.episode_limit = self.env_info["episode_limit"]
-        B, N, dev = self.batch_size, self.n_agents, self.device
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+        B, N, dev, z = self.batch_size, self.n_agents, self.device, self.env._zeros
         self._alive, self._alive_prev = z((B,), torch.uint8), z((B,), torch.uint8)
         self._bs = z((B,), torch.int64)
         self._counts = z((2,), torch.int32)
@@ -321,14 +312,10 @@ class ParallelRunner:
                 bs = self._bs[:int(hc[0])]
             actions = self.mac.select_actions(self.batch, t_ep=k, t_env=self.t_env, bs=bs,
                                               test_mode=test_mode)
-            a = actions.reshape(-1, self.n_agents)   # row j is env bs[j] (j < len(bs) read)
-            if a.device != self.device:
-                a = a.to(self.device)
-            if a.dtype not in _ADT:
-                a = a.to(torch.int64)
-            a = a.contiguous()
+            # row j is env bs[j] (j < len(bs) read)
+            a, adt = as_actions(actions.reshape(-1, self.n_agents), self.device)
             ev, _, dslot = self._ring[k % _RING]
-            rc = step(*fixed, a.data_ptr(), _ADT[a.dtype], a.stride(0), k, dslot, ctypes.byref(r), sh)
+            rc = step(*fixed, a.data_ptr(), adt, a.stride(0), k, dslot, ctypes.byref(r), sh)
             if rc:
                 check(rc, "mapfx_runner_step")
             ev.record(stream)
