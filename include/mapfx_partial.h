@@ -236,6 +236,11 @@ int mapfx_partial_rollout(mapfx_partial_t* h, const mapfx_partial_state* st, int
 /* 1: one launch; 0: a loop of step launches */
 int mapfx_partial_rollout_fused(const mapfx_partial_t* h);
 
+/* The device word ([1], as mapfx_partial_out.err: 0, or 1 + an env given an action outside
+ * 0..4, first report wins) for the calls that take no mapfx_partial_out
+ * (mapfx_runner_rollout, mapfx_runner.h).  NULL (the default): not reported.  Additive. */
+int mapfx_partial_bind_err(mapfx_partial_t* h, int32_t* err);
+
 #ifdef __cplusplus
 }
 #endif

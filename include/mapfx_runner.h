@@ -115,6 +115,46 @@ int mapfx_runner_step(mapfx_partial_t* h, const mapfx_partial_state* st, const m
                       int64_t row_stride, int32_t ts, int32_t* counts_out,
                       const mapfx_episode_rows* rows, void* stream);
 
+/* T runner steps, ts = ts0 .. ts0 + T - 1, of all B envs in one call: the episode loop with
+ * no MAC between the steps.  Additive exports (the ABI version is unchanged).
+ *
+ * The contract is an equivalence.  After the call every byte of every tensor in `rows`,
+ * every array of `rs` (alive / alive_prev as the parity pair, bs, both halves of bs_inv,
+ * counts, ep_return, ep_length, env_steps, env_actions) and every array of `st` equals what
+ * T successive mapfx_runner_step calls at ts = ts0 .. ts0 + T - 1 leave, and `counts_out`
+ * holds what the last of them writes, where row j of call ts's `actions` argument holds the
+ * actions of env bs[j]:
+ *   given actions: actions[ts - ts0][bs[j]] ([T][B][N] of action_dtype).  An action outside
+ *     0..4 skips that env for that step and sets err, as mapfx_runner_step does.
+ *   policy (actions NULL): mapfx_partial_policy's rule (mapfx_partial.h,
+ *     mapfx.rng.partial_policy_actions) on env bs[j] as it stands before call ts, with the
+ *     counter pol->t0 + ts -- the absolute row, so two calls of T / 2 equal one of T.
+ * An env that terminated in step ts - 1 is on the stale list once more: its actions and
+ * one-hot rows at ts are recorded from its resting state, and no other row of it is written.
+ * Like the step form the call keeps stepping the state `st` of an env that is no longer
+ * running (with its stale action, then with stay): only the runner's rows stop.  An
+ * iteration that finds no env running and none stale writes no row.  The mapfx_partial_out
+ * scratch of the step form is not an argument; err goes to the word given to
+ * mapfx_partial_bind_err (none bound: not reported).  A NULL field of `rows` is not
+ * produced; with rows->obs NULL the observation rows are not even built.
+ *
+ * Offered (mapfx_runner_rollout_offered) where mapfx_runner_step is one launch: the wave
+ * kernel with the fused post pass, N <= 64 and sides <= 256; policy mode also needs u8 /
+ * int16 goal tables (H * W <= 32767).  MAPFX_EINVAL before any launch: not offered, T < 1,
+ * ts0 < 0, ts0 + T > rows->max_t, actions and pol both NULL, a bad dtype, a NULL handle,
+ * state, rs (or an rs without bs_inv) or rows.
+ * Asynchronous on `stream`, no allocation, no host synchronisation, graph-capturable in a
+ * single-stream capture: one launch of partial_runner_rollout_kernel, then one of
+ * runner_compact_kernel, which leaves bs / bs_inv / counts as the equivalence demands -- a
+ * run can go on with MAC-driven mapfx_runner_step calls after a scripted prefix. */
+int mapfx_runner_rollout(mapfx_partial_t* h, const mapfx_partial_state* st,
+                         const mapfx_runner_state* rs, int32_t ts0, int32_t T,
+                         const void* actions /* [T][B][N] of action_dtype, or NULL */,
+                         int action_dtype, const mapfx_partial_policy* pol,
+                         int32_t* counts_out, const mapfx_episode_rows* rows, void* stream);
+/* 1 where the call is offered (policy != 0: in policy mode), else 0 */
+int mapfx_runner_rollout_offered(const mapfx_partial_t* h, int policy);
+
 /* n int32 of host memory the device writes directly (hipHostMalloc mapped +
  * coherent): *host_ptr for the host, *dev_ptr for kernels (mapfx_runner_post's
  * counts_out).  Free with mapfx_host_ring_free(host_ptr). */

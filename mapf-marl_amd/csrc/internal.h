@@ -70,6 +70,24 @@ int mapfx_partial_step_runner(mapfx_partial_t* h, const mapfx_partial_state* st,
                               int action_dtype, const mapfx_runner_acts* ra, const mapfx_partial_out* out,
                               float* obs_rows, long long obs_env_stride, const uint8_t* obs_mask,
                               void* stream);
+// The fused launch of mapfx_runner_rollout: T runner steps ts = ra->ts .. ra->ts + T - 1 of
+// every env.  Of `ra`: the actions / one-hot / reward / terminated rows with their strides,
+// ep_state / ep_avail / ep_filled as ROW 0 pointers (the kernel adds (ts + 1) times the time
+// strides below), alive = A[ts0 & 1] and alive_prev = A[(ts0 + 1) & 1] (both rewritten),
+// ep_return, ep_length and cmp_env_steps (+= the envs running before each step but the
+// last: the compaction after the launch adds those).  act_row and the other cmp_* are
+// unused: actions are indexed by env.
+typedef struct mapfx_runner_roll {
+  int max_t;
+  float* obs_rows;     // the observation rows' time row ts0 + 1, NULL: rows are not built
+  long long obs_sb, obs_st;
+  long long state_st, avail_st, filled_st;
+  int32_t* stale_out;  // [E] 0 / -1: env on the last step's stale list; NULL when T == 1
+} mapfx_runner_roll;
+int mapfx_partial_rollout_runner(mapfx_partial_t* h, const mapfx_partial_state* st, int32_t T, const void* actions,
+                                 int action_dtype, const mapfx_partial_policy* pol, const mapfx_runner_acts* ra,
+                                 const mapfx_runner_roll* rr, void* stream);
+int mapfx_partial_runner_rollout_offered(const mapfx_partial_t* h, int policy);
 #ifdef __cplusplus
 }
 

@@ -178,6 +178,15 @@ struct RArgs {
   int8_t* actions;      // [T][E][N] (policy mode), or NULL
 };
 
+// partial_runner_rollout_kernel (mapfx_runner_rollout) on top of RArgs: step k is runner
+// step ts0 + k; the rows the post pass writes at ts + 1 move by these time strides (PArgs.ra
+// holds their row-0 pointers, PArgs.obs_rows row ts0 + 1), none past max_t - 1
+struct RRun {
+  int ts0, max_t;
+  long long obs_st, state_st, avail_st, filled_st;
+  int32_t* stale_out;   // [E] 0 / -1: env on the last step's stale list (T >= 2), or NULL
+};
+
 // where env e's observation rows go ([N][D] floats), or nullptr when not written
 // (partial_kernel: the caller has read obs_mask[e] with the launch's other loads)
 template <bool ROWS = true>
@@ -1046,7 +1055,8 @@ __device__ __forceinline__ int policy_action(const RArgs& ro, int env, int k, in
 // between steps; stale low bits of dep are harmless: every occupant of a cell writes its
 // move before anyone reads it.
 template <int WIN, int KF, int LF, int GDE, bool RUN, int ROLL>
-__device__ __forceinline__ void partial_body(const PGeo& g_, const PArgs& a_, const RArgs& ro, const int blk) {
+__device__ __forceinline__ void partial_body(const PGeo& g_, const PArgs& a_, const RArgs& ro, const RRun& rn,
+                                             const int blk) {
   std::conditional_t<ROLL != 0, PArgs, const PArgs&> a = a_;  // (the rollout advances the outputs)
   PGeo g = g_;
   if constexpr (LF > 0) {  // the fast instances' lane group and K as constants (launch() picks
@@ -1089,7 +1099,11 @@ __device__ __forceinline__ void partial_body(const PGeo& g_, const PArgs& a_, co
   // the prologue ----
   const long long oc_ = has ? oa : 0;
   const int ec_ = env_ok ? env : 0;
-  const bool runner = RUN && a.do_step && a.ra.act_row != nullptr;
+  // RR: the runner's rollout (mapfx_runner_rollout) -- T runner steps of one launch.  Actions
+  // are indexed by env (no act_row map, no compaction workgroup); an env's running / stale
+  // flags and its return stay in registers across the loop
+  constexpr bool RR = RUN && ROLL != 0;
+  const bool runner = RUN && !RR && a.do_step && a.ra.act_row != nullptr;
   const bool post = RUN && a.ra.alive != nullptr;  // the runner's post pass, fused
   const bool nb_carry = a.pnbr && a.pdist && !g.gd32;  // neighbour distances carried
   const uint32_t* bsrc = (const uint32_t*)(a.bits + (g.map_shared ? 0 : (long long)ec_ * g.map_stride));
@@ -1123,10 +1137,12 @@ __device__ __forceinline__ void partial_body(const PGeo& g_, const PArgs& a_, co
   if (a.do_reset && a.reset_mask) rm_raw = a.reset_mask[ec_];
   double epr_raw = 0.0;
   int64_t epl_raw = 0;
+  uint32_t stale_raw = 0;
   if (post) {
     live_raw = a.ra.alive[ec_];
     epr_raw = a.ra.ep_return[ec_];
     epl_raw = a.ra.ep_length[ec_];
+    if constexpr (RR) stale_raw = a.ra.alive_prev[ec_];
   }
   if constexpr (KF > 0 && LF > 0 && ROLL != 2) {  // float32 sqrt(0 .. sq_max) for the K-nearest rows
     if (g.off_sqrt >= 0) {            // (:352 math.sqrt), while the loads are in flight
@@ -1188,6 +1204,14 @@ __device__ __forceinline__ void partial_body(const PGeo& g_, const PArgs& a_, co
   const uint8_t live0 = live_raw != 0 ? 1 : 0;
   const double epr0 = epr_raw;
   const int64_t epl0 = epl_raw;
+  // RR: the env is running before the step (A[ts & 1]) / on the step's stale list (running
+  // before step ts - 1: at entry the other parity half); the return so far, the steps it
+  // ran in this launch, the wave's env steps (all but the last step's: the compaction adds
+  // those)
+  bool live = live0 != 0, stale = stale_raw != 0, stale_last = stale;
+  double epr = epr0;
+  int nlive = 0, wave_steps = 0;
+  (void)live, (void)stale, (void)stale_last, (void)epr, (void)nlive, (void)wave_steps;
   const int gr = q.x, gc = q.y, ir = ip.x, ic = ip.y;
   int r = 0, c = 0, steps = 0, gcost = -1, edge = 0;
   int pd = PD_NONE;  // goal distance of the current cell (carried)
@@ -1305,7 +1329,28 @@ __device__ __forceinline__ void partial_body(const PGeo& g_, const PArgs& a_, co
     }
   };
   const int T = ROLL ? ro.T : 1;
+  // RR: the env's last step in this launch was a full step of an env already terminated --
+  // nobody moved (every agent of a terminated env is done), so its node / edge flags stand
+  bool quiet = !env_ok;
+  (void)quiet;
   for (int k = 0; k < T; ++k) {  // (the step kernel: one pass, no loop is left in its code)
+  const bool term_in = term;
+  (void)term_in;
+  if constexpr (RR) {
+    // A wave none of whose envs is running or stale leaves the loop.  The steps it skips
+    // write no row, and what they do to the env state (the step form steps a terminated env
+    // too, with stay) is known once every env is quiet: each counts the standing collisions
+    // again, advances the step count and stamps it on the agents at their goals.
+    if (!__ballot((env_ok && (live || stale)) || !quiet)) {
+      const int R = T - k;
+      const int esum = group_sum(has ? (int)node + edge : 0, LF > 0 ? LF : g.L);
+      tcur += R;
+      total += R * (esum / 2);
+      if (at_goal) gcost = tcur;
+      stale_last = false;
+      break;
+    }
+  }
   if constexpr (ROLL != 0) {
     // autoreset: a terminated env restarts from init_pos (:125-163) before it is stepped
     const bool rs = ro.autoreset && term;
@@ -1336,6 +1381,29 @@ __device__ __forceinline__ void partial_body(const PGeo& g_, const PArgs& a_, co
       if (has && ro.actions) ro.actions[(long long)k * g.E * N + oa] = (int8_t)act;
     } else if (k > 0) {
       act = has ? decode_raw(araw_n, abyte_n) : 4;
+    }
+    if constexpr (RR) {
+      // the actions / actions_onehot rows at ts of an env on the stale list (a terminated
+      // one is there once more, with the action its resting state gives); an env off it stays
+      if (!stale) {
+        act = 4;
+      } else if (has) {
+        long long v = act;  // the raw value, as the step form records it
+        if (!ro.policy) {
+          const uint32_t w = (abyte_n & 4) ? araw_n.y : araw_n.x;
+          const int b8 = (int)(int8_t)(uint8_t)(w >> ((abyte_n & 3) * 8));
+          v = a.act_dtype == MAPFX_I64   ? act_value((int)araw_n.x, (int)araw_n.y)
+              : a.act_dtype == MAPFX_I32 ? (long long)(int)w
+                                         : (long long)b8;
+        }
+        const long long ts = rn.ts0 + k;
+        if (a.ra.ep_actions) a.ra.ep_actions[(long long)env * a.ra.ep_actions_sb + ts * a.ra.ep_actions_st + ag] = v;
+        if (a.ra.ep_onehot) {
+          float* oh = a.ra.ep_onehot + (long long)env * a.ra.ep_onehot_sb + ts * a.ra.ep_onehot_st + (long long)ag * 5;
+#pragma unroll
+          for (int q = 0; q < 5; ++q) oh[q] = v == q ? 1.0f : 0.0f;
+        }
+      }
     }
     // (policy mode: row stride 0 -- the dummy block again, outside every branch)
     // a GLOBAL load: a flat one also counts on the LDS counter, and the step's next LDS
@@ -1453,7 +1521,9 @@ __device__ __forceinline__ void partial_body(const PGeo& g_, const PArgs& a_, co
         }
       }
       PST(7);
+      if constexpr (RR) quiet = term_in;
     } else {
+      if constexpr (RR) quiet = false;
       if (ag == 0 && a.err) atomicCAS(a.err, 0, env + 1);
       if (ag == 0 && a.reward) a.reward[env] = 0.0;
     }
@@ -1494,32 +1564,51 @@ __device__ __forceinline__ void partial_body(const PGeo& g_, const PArgs& a_, co
   }
   if (post && env_ok) {  // runner_post_kernel (runner.hip) for a running env, fused
     const mapfx_runner_acts& ra = a.ra;
-    if (live0) {
+    // the step's time row and the rows at ts + 1 (the step form: as the call gave them)
+    int ts = ra.ts;
+    float* ep_state = ra.ep_state;
+    int32_t* ep_avail = ra.ep_avail;
+    int64_t* ep_filled = ra.ep_filled;
+    if constexpr (RR) {
+      ts = rn.ts0 + k;
+      const bool nxt = ts + 1 < rn.max_t;
+      ep_state = nxt && ra.ep_state ? ra.ep_state + (long long)(ts + 1) * rn.state_st : nullptr;
+      ep_avail = nxt && ra.ep_avail ? ra.ep_avail + (long long)(ts + 1) * rn.avail_st : nullptr;
+      ep_filled = nxt && ra.ep_filled ? ra.ep_filled + (long long)(ts + 1) * rn.filled_st : nullptr;
+    }
+    if (RR ? live : live0 != 0) {
       if (ag == 0) {
-        if (ra.ep_reward) ra.ep_reward[(long long)env * ra.ep_reward_sb + (long long)ra.ts * ra.ep_reward_st] = (float)Rsum;
+        if (ra.ep_reward) ra.ep_reward[(long long)env * ra.ep_reward_sb + (long long)ts * ra.ep_reward_st] = (float)Rsum;
         // env_terminated = terminated and not info.get("episode_limit") (parallel_runner.py:146-150):
         // MARL_PARTIAL's info has no "episode_limit" key
-        if (ra.ep_term) ra.ep_term[(long long)env * ra.ep_term_sb + (long long)ra.ts * ra.ep_term_st] = term ? 1 : 0;
-        ra.ep_return[env] = epr0 + Rsum;
-        ra.ep_length[env] = epl0 + 1;
-        if (!ra.cmp_bs) ra.alive[env] = term ? 0 : 1;  // (fused compaction: A_out below)
-        if (ra.ep_state) {  // update(pre_transition_data, bs, ts + 1): state, avail, filled
-          float* d = ra.ep_state + (long long)env * ra.ep_state_sb;
+        if (ra.ep_term) ra.ep_term[(long long)env * ra.ep_term_sb + (long long)ts * ra.ep_term_st] = term ? 1 : 0;
+        if constexpr (RR) {  // (stored once, after the loop)
+          epr = epr + Rsum;
+          ++nlive;
+        } else {
+          ra.ep_return[env] = epr0 + Rsum;
+          ra.ep_length[env] = epl0 + 1;
+          if (!ra.cmp_bs) ra.alive[env] = term ? 0 : 1;  // (fused compaction: A_out below)
+        }
+        if (ep_state) {  // update(pre_transition_data, bs, ts + 1): state, avail, filled
+          float* d = ep_state + (long long)env * ra.ep_state_sb;
           d[0] = (float)total;
           d[1] = (float)tcur;
           d[2] = (float)gsum;
         }
-        if (ra.ep_filled) ra.ep_filled[(long long)env * ra.ep_filled_sb] = 1;
+        if (ep_filled) ep_filled[(long long)env * ra.ep_filled_sb] = 1;
       }
-      if (has && ra.ep_avail) {
-        int32_t* d = ra.ep_avail + (long long)env * ra.ep_avail_sb + ag * 5;
+      if (has && ep_avail) {
+        int32_t* d = ep_avail + (long long)env * ra.ep_avail_sb + ag * 5;
 #pragma unroll
         for (int k = 0; k < 5; ++k) d[k] = (int32_t)((am >> k) & 1u);
       }
     }
     // alive_prev: the stale list for the separate compaction, or, with the compaction
     // fused (cmp_bs), A[(ts + 1) & 1] = running after this step, written for every env
-    if (ag == 0) ra.alive_prev[env] = ra.cmp_bs ? (uint8_t)(live0 && !term ? 1 : 0) : live0;
+    // (the rollout: both parity halves once, after the loop)
+    if constexpr (!RR)
+      if (ag == 0) ra.alive_prev[env] = ra.cmp_bs ? (uint8_t)(live0 && !term ? 1 : 0) : live0;
   }
   uint2 nb1 = make_uint2(0u, 0u);
   if constexpr (ROLL != 2) {  // (a rollout without the rows builds and stages none of this)
@@ -1541,7 +1630,9 @@ __device__ __forceinline__ void partial_body(const PGeo& g_, const PArgs& a_, co
   constexpr int WW = WIN * WIN;
   constexpr int DF = (KF > 0 && LF > 0) ? 2 * WW + NF * KF : 1;  // fast-path row length
   float o[DF];
-  float* const my_obs = (env_ok && omask) ? obs_env_nomask<RUN>(a, env, (KF > 0 && LF > 0) ? DF : g.D, N) : nullptr;
+  // (the runner's rollout: the rows at ts + 1 of the envs running before this step)
+  const bool om = RR ? (live && rn.ts0 + k + 1 < rn.max_t) : omask;
+  float* const my_obs = (env_ok && om) ? obs_env_nomask<RUN>(a, env, (KF > 0 && LF > 0) ? DF : g.D, N) : nullptr;
   // Staged copy-out (fast path): the rows of the envs of a staging group (the whole wave,
   // or each half of it) are one contiguous run of the destination (a.obs), or one run
   // per env (EpisodeBatch rows): each run is staged in LDS as its byte image, at the
@@ -1764,6 +1855,13 @@ __device__ __forceinline__ void partial_body(const PGeo& g_, const PArgs& a_, co
     if (a.obs) a.obs += (long long)g.E * N * g.D;
     if (a.state) a.state += 3ll * g.E;
     if (a.avail) a.avail += (long long)g.E * N;
+    if constexpr (RR) {  // the next step's time row and flags
+      if (a.obs_rows) a.obs_rows += rn.obs_st;
+      if (k + 1 < T) wave_steps += __popcll(__ballot(env_ok && ag == 0 && live));
+      stale_last = stale;
+      stale = live;
+      live = live && !term;
+    }
   }
   }  // for k
   if constexpr (ROLL != 0) {  // the state leaves once, after the last step
@@ -1771,6 +1869,25 @@ __device__ __forceinline__ void partial_body(const PGeo& g_, const PArgs& a_, co
     if (has && nb_carry)
       ((uint2*)a.pnbr)[oa] = make_uint2(((uint32_t)nbd0 & 0xFFFFu) | ((uint32_t)nbd1 << 16),
                                         ((uint32_t)nbd2 & 0xFFFFu) | ((uint32_t)nbd3 << 16));
+  }
+  if constexpr (RR) {
+    // The runner's bookkeeping as T runner steps leave it: A[(ts + 1) & 1] = running after
+    // the last step ts, A[ts & 1] = running before it (`alive` is the half of ts0's parity);
+    // returns / lengths of the envs that ran; the stale list of the last step as flags
+    // where its row map goes (the compaction that follows turns them into rows)
+    if (post && env_ok && ag == 0) {
+      const mapfx_runner_acts& ra = a.ra;
+      const bool odd = (T & 1) != 0;
+      ra.alive[env] = (odd ? stale : live) ? 1 : 0;
+      ra.alive_prev[env] = (odd ? live : stale) ? 1 : 0;
+      if (nlive) {
+        ra.ep_return[env] = epr;
+        ra.ep_length[env] = epl0 + nlive;
+      }
+      if (rn.stale_out) rn.stale_out[env] = stale_last ? 0 : -1;
+    }
+    if (post && lane64 == 0 && wave_steps)
+      atomicAdd((unsigned long long*)a.ra.cmp_env_steps, (unsigned long long)wave_steps);
   }
   PST(12);
 #ifdef PARTIAL_STAMPS
@@ -1790,14 +1907,22 @@ __global__ void __launch_bounds__(64 * PARTIAL_MAX_WPB) partial_kernel(PGeo g_, 
       return;
     }
   }
-  partial_body<WIN, KF, LF, GDE, RUN, 0>(g_, a, RArgs{}, blk);
+  partial_body<WIN, KF, LF, GDE, RUN, 0>(g_, a, RArgs{}, RRun{}, blk);
 }
 
 // T steps of every env in one launch (mapfx_partial_rollout).  OBS false: the trajectory
 // has no observation rows, and WIN / KF play no part.
 template <int WIN, int KF, int LF, int GDE, bool OBS>
 __global__ void __launch_bounds__(64 * PARTIAL_MAX_WPB) partial_rollout_kernel(PGeo g_, PArgs a, RArgs ro) {
-  partial_body<WIN, KF, LF, GDE, false, OBS ? 1 : 2>(g_, a, ro, (int)blockIdx.x);
+  partial_body<WIN, KF, LF, GDE, false, OBS ? 1 : 2>(g_, a, ro, RRun{}, (int)blockIdx.x);
+}
+
+// T runner steps of every env in one launch (mapfx_runner_rollout): the rollout's loop with
+// the runner's actions rows, post pass and flags (RUN) per step.  OBS false: rows->obs NULL.
+template <int WIN, int KF, int LF, int GDE, bool OBS>
+__global__ void __launch_bounds__(64 * PARTIAL_MAX_WPB) partial_runner_rollout_kernel(PGeo g_, PArgs a, RArgs ro,
+                                                                                      RRun rn) {
+  partial_body<WIN, KF, LF, GDE, true, OBS ? 1 : 2>(g_, a, ro, rn, (int)blockIdx.x);
 }
 
 // A goal-table rebuild makes the carried distances stale: pdist of every (masked) env
@@ -1935,6 +2060,7 @@ struct mapfx_partial_t {
   double* bonus_lut;
   int device;
   int no_nbcarry;  // diagnostic builds (MAPFX_PARTIAL_DIAG_ENV) only: ignore the state's pnbr
+  int32_t* err;    // mapfx_partial_bind_err: where the calls without a mapfx_partial_out report
 };
 
 namespace {
@@ -2030,6 +2156,40 @@ RolloutFn pick_roll(int win, int K, int L, int tw, bool obs) {
     case 5: return partial_rollout_kernel<5, 0, 0, 0, true>;
     case 7: return partial_rollout_kernel<7, 0, 0, 0, true>;
     case 9: return partial_rollout_kernel<9, 0, 0, 0, true>;
+  }
+  return nullptr;
+}
+
+// partial_runner_rollout_kernel's instances: with the rows the five fast shapes of the
+// runner's step at u8 / int16 tables and the six generic windows (which also take the fast
+// shapes' int32 tables); without the rows one per fast lane group (table width at run time)
+// and one generic.
+using RunRollFn = void (*)(PGeo, PArgs, RArgs, RRun);
+template <int WIN, int LF>
+RunRollFn pick_run_roll_fast(int tw) {
+  return tw == 1 ? partial_runner_rollout_kernel<WIN, 5, LF, 1, true> : partial_runner_rollout_kernel<WIN, 5, LF, 2, true>;
+}
+RunRollFn pick_run_roll(int win, int K, int L, int tw, bool obs) {
+  if (!obs) {
+    if (L == 8) return partial_runner_rollout_kernel<0, 5, 8, 0, false>;
+    if (L == 16) return partial_runner_rollout_kernel<0, 5, 16, 0, false>;
+    if (L == 32) return partial_runner_rollout_kernel<0, 5, 32, 0, false>;
+    return partial_runner_rollout_kernel<0, 0, 0, 0, false>;
+  }
+  if (tw != 0) {
+    if (K == 5 && win == 5 && L == 16) return pick_run_roll_fast<5, 16>(tw);
+    if (K == 5 && win == 5 && L == 8) return pick_run_roll_fast<5, 8>(tw);
+    if (K == 5 && win == 5 && L == 32) return pick_run_roll_fast<5, 32>(tw);
+    if (K == 5 && win == 3 && L == 16) return pick_run_roll_fast<3, 16>(tw);
+    if (K == 5 && win == 7 && L == 16) return pick_run_roll_fast<7, 16>(tw);
+  }
+  switch (win) {
+    case 0: return partial_runner_rollout_kernel<0, 0, 0, 0, true>;
+    case 1: return partial_runner_rollout_kernel<1, 0, 0, 0, true>;
+    case 3: return partial_runner_rollout_kernel<3, 0, 0, 0, true>;
+    case 5: return partial_runner_rollout_kernel<5, 0, 0, 0, true>;
+    case 7: return partial_runner_rollout_kernel<7, 0, 0, 0, true>;
+    case 9: return partial_runner_rollout_kernel<9, 0, 0, 0, true>;
   }
   return nullptr;
 }
@@ -2308,6 +2468,11 @@ int mapfx_partial_create(const mapfx_partial_cfg* cfg, mapfx_partial_t** out) {
         rc = check_hip(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize,
                                            gr.lds * gr.wpb),
                        "hipFuncSetAttribute(partial_rollout_kernel LDS)");
+      const RunRollFn rfn = pick_run_roll(g.win, g.K, g.L, g.gd8 ? 1 : g.gd32 ? 0 : 2, obs != 0);
+      if (!rc && rfn && gr.lds * gr.wpb > 64 * 1024)
+        rc = check_hip(hipFuncSetAttribute((const void*)rfn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           gr.lds * gr.wpb),
+                       "hipFuncSetAttribute(partial_runner_rollout_kernel LDS)");
     }
   }
   if (rc) return rc;
@@ -2601,6 +2766,79 @@ int mapfx_partial_rollout(mapfx_partial_t* h, const mapfx_partial_state* st, int
   const int waves = (g.E + gr.EPW - 1) / gr.EPW;
   return launch_kernel(fn, dim3((waves + gr.wpb - 1) / gr.wpb), dim3(64 * gr.wpb), gr.lds * gr.wpb,
                        (hipStream_t)stream, nullptr, nullptr, "partial_rollout_kernel launch", NOTED, gr, a, ro);
+}
+
+int mapfx_partial_bind_err(mapfx_partial_t* h, int32_t* err) {
+  if (!h) return perr(MAPFX_EINVAL, "NULL handle");
+  h->err = err;
+  return MAPFX_OK;
+}
+
+int mapfx_partial_runner_rollout_offered(const mapfx_partial_t* h, int policy) {
+  return h && !h->geo.big && !(policy && h->geo.gd32) ? 1 : 0;
+}
+
+// The fused launch of mapfx_runner_rollout (runner.hip, which checks the runner's half of
+// the arguments and runs the compaction after it); internal.h
+int mapfx_partial_rollout_runner(mapfx_partial_t* h, const mapfx_partial_state* st, int32_t T, const void* actions,
+                                 int action_dtype, const mapfx_partial_policy* pol, const mapfx_runner_acts* ra,
+                                 const mapfx_runner_roll* rr, void* stream) {
+  if (!h) return perr(MAPFX_EINVAL, "NULL handle");
+  int rc = check_state(h, st);
+  if (rc) return rc;
+  if (!ra || !rr || !ra->alive || !ra->alive_prev) return perr(MAPFX_EINVAL, "mapfx_runner_rollout: NULL runner rows");
+  if (T < 1) return perr(MAPFX_EINVAL, "mapfx_runner_rollout: T must be >= 1");
+  if (!actions && !pol) return perr(MAPFX_EINVAL, "mapfx_runner_rollout: actions or a policy is required");
+  const bool policy = actions == nullptr;
+  if (!policy && (action_dtype < MAPFX_I8 || action_dtype > MAPFX_I64)) return perr(MAPFX_EINVAL, "bad action_dtype");
+  const PGeo& g = h->geo;
+  if (!mapfx_partial_runner_rollout_offered(h, policy ? 1 : 0))
+    return perr(MAPFX_EINVAL,
+                policy ? "mapfx_runner_rollout: the on-device policy needs the wave kernel (N <= 64, sides <= 256) "
+                         "and u8 / int16 goal tables (H * W <= 32767)"
+                       : "mapfx_runner_rollout: offered on the wave kernel only (N <= 64, sides <= 256)");
+  if (g.E == 0) return MAPFX_OK;
+  const bool obs = rr->obs_rows != nullptr;
+  const RunRollFn fn = pick_run_roll(g.win, g.K, g.L, g.gd8 ? 1 : g.gd32 ? 0 : 2, obs);
+  if (!fn) return perr(MAPFX_EINVAL, "obs_window must be one of 0, 1, 3, 5, 7, 9");
+  PArgs a;
+  memset(&a, 0, sizeof(a));
+  fill_state(a, st);
+  a.bonus_lut = h->bonus_lut;
+  if (h->no_nbcarry) a.pnbr = nullptr;
+  a.actions = policy ? (const void*)st->pos : actions;  // (policy: the prologue's dummy load)
+  a.act_dtype = policy ? MAPFX_I8 : action_dtype;
+  a.do_step = 1;
+  a.err = h->err;
+  a.obs_rows = rr->obs_rows;
+  a.obs_env_stride = rr->obs_sb;
+  a.ra = *ra;
+  a.ra.act_row = nullptr;
+  a.ra.cmp_bs = nullptr;
+  RArgs ro;
+  memset(&ro, 0, sizeof(ro));
+  ro.T = T;
+  ro.policy = policy ? 1 : 0;
+  if (policy) {
+    ro.t0 = pol->t0 + ra->ts;  // the counter is the absolute row pol->t0 + ts
+    ro.seed = pol->seed;
+    ro.eps_q = pol->eps_q;
+  }
+  ro.env_offset = (long long)h->cfg.env_offset;
+  RRun rn;
+  memset(&rn, 0, sizeof(rn));
+  rn.ts0 = ra->ts;
+  rn.max_t = rr->max_t;
+  rn.obs_st = rr->obs_st;
+  rn.state_st = rr->state_st;
+  rn.avail_st = rr->avail_st;
+  rn.filled_st = rr->filled_st;
+  rn.stale_out = rr->stale_out;
+  const PGeo& gr = h->geo_roll[obs ? 1 : 0];
+  const int waves = (g.E + gr.EPW - 1) / gr.EPW;
+  return launch_kernel(fn, dim3((waves + gr.wpb - 1) / gr.wpb), dim3(64 * gr.wpb), gr.lds * gr.wpb,
+                       (hipStream_t)stream, nullptr, nullptr, "partial_runner_rollout_kernel launch", NOTED, gr, a,
+                       ro, rn);
 }
 
 }  // extern "C"

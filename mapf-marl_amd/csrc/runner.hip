@@ -133,7 +133,13 @@ __global__ void __launch_bounds__(RB) runner_post_kernel(mapfx_runner_state rs, 
 // counts = {len(bs), number alive}.  One workgroup: per-thread chunk counts, a
 // shuffle scan inside each wave and one barrier for the 16 wave totals.
 constexpr int CT = 1024;
-__global__ void __launch_bounds__(CT) runner_compact_kernel(mapfx_runner_state rs, int32_t* counts_out) {
+// A second workgroup (mapfx_runner_rollout only, stale_map not NULL): the row map of a stale
+// list given as flags in stale_map (>= 0: on it), turned into rows in place -- the same scan,
+// nothing else written.
+__global__ void __launch_bounds__(CT) runner_compact_kernel(mapfx_runner_state rs, int32_t* counts_out,
+                                                            int32_t* stale_map) {
+  const bool second = blockIdx.x == 1;
+  const auto listed = [&](int b) { return second ? stale_map[b] >= 0 : rs.alive_prev[b] != 0; };
   __shared__ int wsum[CT / 64];
   __shared__ int wsum_a[CT / 64];
   const int chunk = (rs.B + CT - 1) / CT;
@@ -141,7 +147,7 @@ __global__ void __launch_bounds__(CT) runner_compact_kernel(mapfx_runner_state r
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   int c = 0, ca = 0;
   for (int b = lo; b < hi; ++b) {
-    c += rs.alive_prev[b] ? 1 : 0;
+    c += listed(b) ? 1 : 0;
     ca += rs.alive[b] ? 1 : 0;
   }
   int x = c;  // inclusive scan over the wave's lanes
@@ -165,6 +171,10 @@ __global__ void __launch_bounds__(CT) runner_compact_kernel(mapfx_runner_state r
     total_a += wsum_a[i];
   }
   int o = off + x - c;  // exclusive prefix of this thread's chunk
+  if (second) {
+    for (int b = lo; b < hi; ++b) stale_map[b] = listed(b) ? o++ : -1;
+    return;  // (uniform over the workgroup)
+  }
   for (int b = lo; b < hi; ++b) {
     const bool in = rs.alive_prev[b] != 0;
     if (rs.bs_inv) rs.bs_inv[b] = in ? o : -1;  // where the next MAC call puts env b's row
@@ -234,7 +244,7 @@ int mapfx_runner_post(const mapfx_runner_state* rs, const uint8_t* terminated,
                      "runner_post_kernel launch", QUIET, *rs, terminated, *out, (int)ts, *rows);
   if (rc) return rc;
   return launch_kernel(runner_compact_kernel, dim3(1), dim3(CT), 0, (hipStream_t)stream, nullptr, nullptr,
-                       "runner_compact_kernel launch", QUIET, *rs, counts_out);
+                       "runner_compact_kernel launch", QUIET, *rs, counts_out, (int32_t*)nullptr);
 }
 
 int mapfx_runner_step(mapfx_partial_t* h, const mapfx_partial_state* st, const mapfx_partial_out* out,
@@ -308,6 +318,78 @@ int mapfx_runner_step(mapfx_partial_t* h, const mapfx_partial_state* st, const m
   mapfx_episode_rows r2 = *rows;
   r2.obs = nullptr;
   return mapfx_runner_post(rs, st->terminated, out, ts, counts_out, &r2, stream);
+}
+
+int mapfx_runner_rollout_offered(const mapfx_partial_t* h, int policy) {
+  return mapfx_partial_runner_rollout_offered(h, policy);
+}
+
+int mapfx_runner_rollout(mapfx_partial_t* h, const mapfx_partial_state* st, const mapfx_runner_state* rs,
+                         int32_t ts0, int32_t T, const void* actions, int action_dtype,
+                         const mapfx_partial_policy* pol, int32_t* counts_out, const mapfx_episode_rows* rows,
+                         void* stream) {
+  if (!h) return perr(MAPFX_EINVAL, "runner_rollout: NULL handle");
+  int rc = check_rs(rs);
+  if (rc) return rc;
+  if (!rs->bs_inv) return perr(MAPFX_EINVAL, "runner_rollout: the runner state needs bs_inv");
+  if (!st || !rows) return perr(MAPFX_EINVAL, "runner_rollout: NULL state / rows");
+  if (T < 1 || ts0 < 0 || (int64_t)ts0 + T > rows->max_t)
+    return perr(MAPFX_EINVAL, "runner_rollout: steps ts0 .. ts0 + T - 1 must lie inside the batch, T >= 1");
+  if (!actions && !pol) return perr(MAPFX_EINVAL, "runner_rollout: actions or a policy is required");
+  if (actions && (action_dtype < MAPFX_I8 || action_dtype > MAPFX_I64))
+    return perr(MAPFX_EINVAL, "runner_rollout: bad dtype");
+  // the parity pair as mapfx_runner_step uses it: A[ts & 1] = running before step ts
+  const int par0 = ts0 & 1, ts_end = ts0 + T - 1, par_end = ts_end & 1;
+  mapfx_runner_acts ra;
+  memset(&ra, 0, sizeof ra);
+  ra.ts = ts0;
+  ra.ep_actions = rows->actions;
+  ra.ep_actions_sb = rows->actions_sb;
+  ra.ep_actions_st = rows->actions_st;
+  ra.ep_onehot = rows->onehot;
+  ra.ep_onehot_sb = rows->onehot_sb;
+  ra.ep_onehot_st = rows->onehot_st;
+  ra.alive = par0 ? rs->alive_prev : rs->alive;
+  ra.alive_prev = par0 ? rs->alive : rs->alive_prev;
+  ra.ep_return = rs->ep_return;
+  ra.ep_length = rs->ep_length;
+  ra.cmp_env_steps = rs->env_steps;
+  ra.ep_reward = rows->reward;
+  ra.ep_reward_sb = rows->reward_sb;
+  ra.ep_reward_st = rows->reward_st;
+  ra.ep_term = rows->terminated;
+  ra.ep_term_sb = rows->terminated_sb;
+  ra.ep_term_st = rows->terminated_st;
+  ra.ep_state = rows->state;
+  ra.ep_state_sb = rows->state_sb;
+  ra.ep_avail = rows->avail;
+  ra.ep_avail_sb = rows->avail_sb;
+  ra.ep_filled = rows->filled;
+  ra.ep_filled_sb = rows->filled_sb;
+  mapfx_runner_roll rr;
+  memset(&rr, 0, sizeof rr);
+  rr.max_t = rows->max_t;
+  rr.obs_rows = rows->obs ? rows->obs + (int64_t)(ts0 + 1) * rows->obs_st : nullptr;
+  rr.obs_sb = rows->obs_sb;
+  rr.obs_st = rows->obs_st;
+  rr.state_st = rows->state_st;
+  rr.avail_st = rows->avail_st;
+  rr.filled_st = rows->filled_st;
+  // T >= 2: the row map of the last step's stale list (what step ts_end - 1's compaction
+  // leaves in bs_inv[ts_end & 1]) -- the kernel writes the list as flags, the compaction's
+  // second workgroup turns them into rows
+  int32_t* const stale_map = T >= 2 ? rs->bs_inv + (int64_t)par_end * rs->B : nullptr;
+  rr.stale_out = stale_map;
+  if ((rc = mapfx_partial_rollout_runner(h, st, T, actions, action_dtype, pol, &ra, &rr, stream))) return rc;
+  if (rs->B == 0) return MAPFX_OK;
+  // what step ts_end's compaction leaves: bs / counts of A[ts_end & 1] (running before the
+  // last step), its row map in the other half of bs_inv, env_steps += its length
+  mapfx_runner_state r2 = *rs;
+  r2.alive_prev = par_end ? rs->alive_prev : rs->alive;
+  r2.alive = r2.alive_prev;  // counts[1] = len(bs), as the fused step reports it
+  r2.bs_inv = rs->bs_inv + (int64_t)(par_end ^ 1) * rs->B;
+  return launch_kernel(runner_compact_kernel, dim3(stale_map ? 2 : 1), dim3(CT), 0, (hipStream_t)stream, nullptr,
+                       nullptr, "runner_compact_kernel launch", QUIET, r2, counts_out, stale_map);
 }
 
 int mapfx_host_ring_alloc(int32_t n, int32_t** host_ptr, int32_t** dev_ptr) {

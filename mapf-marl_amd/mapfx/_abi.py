@@ -122,7 +122,8 @@ EXPORTS = ("mapfx_abi_version", "mapfx_last_error", "mapfx_build_id", "mapfx_las
            "mapfx_primal_act", "mapfx_primal_act_timed", "mapfx_primal_observe",
            "mapfx_primal_blocking_count",
            "mapfx_primal_blocking", "mapfx_primal_generate", "mapfx_runner_begin", "mapfx_runner_actions", "mapfx_runner_post",
-           "mapfx_runner_step", "mapfx_host_ring_alloc", "mapfx_host_ring_free")
+           "mapfx_runner_step", "mapfx_host_ring_alloc", "mapfx_host_ring_free",
+           "mapfx_partial_bind_err", "mapfx_runner_rollout", "mapfx_runner_rollout_offered")
 
 
 class ERows(ctypes.Structure):  # include/mapfx_runner.h mapfx_episode_rows
@@ -198,6 +199,10 @@ def _load():
         "mapfx_runner_post": (c_i32, [P(RState), c_vp, P(POut), c_i32, c_vp, P(ERows), c_vp]),
         "mapfx_runner_step": (c_i32, [c_vp, P(PState), P(POut), P(RState), c_vp, c_i32, c_i64, c_i32,
                                       c_vp, P(ERows), c_vp]),
+        "mapfx_partial_bind_err": (c_i32, [c_vp, c_vp]),
+        "mapfx_runner_rollout": (c_i32, [c_vp, P(PState), P(RState), c_i32, c_i32, c_vp, c_i32,
+                                         P(PPolicy), c_vp, P(ERows), c_vp]),
+        "mapfx_runner_rollout_offered": (c_i32, [c_vp, c_i32]),
         "mapfx_host_ring_alloc": (c_i32, [c_i32, P(c_vp), P(c_vp)]),
         "mapfx_host_ring_free": (None, [c_vp]),
     }

@@ -84,6 +84,15 @@ def partial_policy_actions(seed, env_ids, t, eps_q, avail, pd, d):
     return np.where(explore, (u % np.uint64(5)).astype(np.int64), greedy).astype(np.int8)
 
 
+def runner_policy_seed(seed, run):
+    """The policy seed of run number `run` of ParallelRunner.collect:
+    splitmix64(seed ^ run * K_T) -- a pure function of (seed, run), so every run draws its
+    own random words (the policy's counter restarts at 0 with every episode) and a run can
+    be replayed from its number."""
+    return int(splitmix64(np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF)
+                          ^ _mul(np.uint64(int(run) & 0xFFFFFFFFFFFFFFFF), K_T)))
+
+
 def cell_keys(seed, env_ids, n_cells, stream):
     """Per-(env, cell) uint64 keys of stream `stream` (obstacles, starts, goals)."""
     env = np.asarray(env_ids, dtype=np.int64).astype(np.uint64)[:, None]

@@ -30,6 +30,10 @@ with (episode_buffer.py:186-190); `args.runner_exact_bs` passes the exact-length
 list instead (one host sync per step, for stochastic action selectors whose RNG
 consumption must follow the reference's).
 
+`collect()` is a run with no MAC at all: the whole episode loop as one launch
+(mapfx_runner_rollout), the actions from the on-device policy or a given table, the
+batch, t_env and the stats as `run()` leaves them.
+
 Per-env instances: every reset draws each env's scenario like
 MARL_PARTIAL_ENV.__setup_agent (:896-920: random.randint(1, 25) then
 random.sample of the scen lines), from a per-env `random.Random(seed + e)` stream
@@ -55,6 +59,7 @@ from ._base import DTYPES as _ADT    # noqa: F401  (tools/runner_host_probe.py r
 from ._base import as_actions
 from .maps import draw_scen, load_map, load_scen_table, read_scen
 from .partial import MarlPartialBatch
+from .rng import runner_policy_seed
 
 _ROW_DTYPES = {"obs": torch.float32, "state": torch.float32, "avail_actions": torch.int32,
                "actions": torch.int64, "actions_onehot": torch.float32, "reward": torch.float32,
@@ -123,6 +128,9 @@ class ParallelRunner:
             starts, goals = self._draw()
         self.env = MarlPartialBatch(starts, goals, grids=self.grid[None], device=self.device, **ea)
         self._loaded = (starts.tobytes(), goals.tobytes())
+        # collect(): mapfx_runner_rollout takes no mapfx_partial_out, its invalid-action
+        # report goes to the env's err word like the step's
+        check(lib.mapfx_partial_bind_err(self.env._h, ptr(self.env.err)), "mapfx_partial_bind_err")
         if self._device_draw:
             self.env.set_scenarios(lines, n_lines, seed=seed)
         self.env_info = {"state_shape": 3, "obs_shape": self.env.obs_dim, "n_actions": 5,
@@ -321,7 +329,65 @@ class ParallelRunner:
             ev.record(stream)
             k += 1
         self.t = k
-        # the run's totals: one transfer at the end
+        return self._finish(test_mode)
+
+    def collect(self, eps=0.0, seed=None, actions=None, test_mode=False, chunk=None):
+        """One run with no MAC: the episode loop as one launch (mapfx_runner_rollout), the
+        actions from the on-device policy -- each agent descends its shortest path, a
+        fraction `eps` of the moves uniform random (eps_q = round(eps * 2**32): eps=1.0 is
+        PyMARL's initial epsilon, eps=0.0 the shortest-path baseline; rng.partial_policy_actions
+        restates it, keyed by rng.runner_policy_seed(seed, run number), seed=None: args.seed)
+        -- or from `actions`, a [max_t, B, N] int8 / int32 / int64 device tensor indexed by
+        env.  The EpisodeBatch, t_env, the returns and the logged stats are those of `run()`
+        with a MAC that returns the same actions.  chunk: steps per call (None: all max_t
+        in one; a tuple: the successive call lengths).  Nothing is read on the host before
+        the run's totals.  ValueError where the fused call is not offered (N > 64 or a side
+        > 256; the policy also needs H * W <= 32767): use run() with a MAC there."""
+        env = self.env
+        policy = actions is None
+        if not lib.mapfx_runner_rollout_offered(env._h, 1 if policy else 0):
+            raise ValueError(
+                "collect: the one-launch episode loop runs on the wave kernel only (n_agents <= 64 "
+                "and map sides <= 256%s); this runner has n_agents = %d on a %d x %d map"
+                % ("; the on-device policy also needs H * W <= 32767" if policy else "",
+                   self.n_agents, self.grid.shape[0], self.grid.shape[1]))
+        self.reset()
+        r, max_t = self._erows, int(self._erows.max_t)
+        if policy:
+            if not 0.0 <= float(eps) <= 1.0:
+                raise ValueError("eps must be in 0..1")
+            base = int(getattr(self.args, "seed", 0) or 0) if seed is None else int(seed)
+            pol = _abi.PPolicy(seed=runner_policy_seed(base, self._episode - 1),
+                               eps_q=int(round(float(eps) * 2 ** 32)), t0=0)
+            a, adt, polp = None, 0, ctypes.byref(pol)
+        else:
+            a, adt = as_actions(actions, self.device, (max_t, self.batch_size, self.n_agents))
+            polp = None
+        if chunk is None:
+            chunks = [max_t]
+        elif isinstance(chunk, (tuple, list)):
+            chunks = [int(c) for c in chunk]
+        else:
+            chunks = [min(int(chunk), max_t - t) for t in range(0, max_t, int(chunk))]
+        if any(c < 1 for c in chunks) or sum(chunks) != max_t:
+            raise ValueError("chunk: the call lengths must be >= 1 and add up to max_t = %d" % max_t)
+        sh = torch.cuda.current_stream(self.device).cuda_stream
+        esz = a.element_size() * self.batch_size * self.n_agents if a is not None else 0
+        ts = 0
+        for c in chunks:
+            rc = lib.mapfx_runner_rollout(env._h, ctypes.byref(env._state), ctypes.byref(self._rs),
+                                          ts, c, a.data_ptr() + ts * esz if a is not None else None,
+                                          adt, polp, None, ctypes.byref(r), sh)
+            if rc:
+                check(rc, "mapfx_runner_rollout")
+            ts += c
+        self.t = ts
+        return self._finish(test_mode)
+
+    def _finish(self, test_mode):
+        """The end of a run (:175-204): t_env, returns, stats and the log, from the
+        device's totals -- one transfer."""
+        env = self.env
         env_steps = int(self._env_steps.item())
         # an env given an action outside 0..4 was not stepped (its rows say reward 0):
         # the reference asserts at marl_partial.py:177
