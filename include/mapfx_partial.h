@@ -217,6 +217,55 @@ typedef struct mapfx_partial_traj {
  * call returns MAPFX_EINVAL. */
 typedef struct mapfx_partial_policy { uint64_t seed; uint64_t eps_q; int32_t t0; } mapfx_partial_policy;
 
+/* The policy's rule: a setting of the handle (like mapfx_partial_bind_err), read when a
+ * policy-mode call is enqueued -- under graph capture it is captured with the launch -- by
+ * mapfx_partial_rollout (rows built or not) and mapfx_runner_rollout alike.  Additive.
+ *
+ * MAPFX_POLICY_DESCENT (the default): the rule above; every agent ignores the others.
+ *
+ * MAPFX_POLICY_PIBT: one-step priority inheritance with backtracking; no step it drives
+ * creates an edge collision, nor a node collision except among agents that already shared
+ * a cell.  u, pd, d_m and ok_m as above, p_a the agent's cell, v_{a,m} its neighbour m,
+ * explore_a = (u_a >> 32) < eps_q.  The candidates of agent a, in order:
+ *   pd_a < 0                            stay alone
+ *   called at top level and explore_a   [u_a % 5, if that is a move m < 4 with ok_m], stay
+ *   otherwise (a pushed agent always)   the ok_m moves and stay as (pd_a, 4), ascending (d, m)
+ * Agents are planned in ascending (pd_a == 0, (a - t) mod N) -- t = t0 + k as an unsigned
+ * 32-bit value, the non-negative modulus -- so agents off their goals come first and the
+ * index priority rotates every step; one still undecided at its turn runs PLAN(a, none).
+ * PLAN(a, parent), for each candidate (m, v):
+ *   1. v is claimed: skip.     2. v == p_parent: skip (no swap).
+ *   3. m != 4: U = the undecided agents b != a with p_b == v; |U| >= 2: skip.
+ *   4. claim v; a is decided with action m.
+ *   5. |U| == 1: PLAN(b, a); false (b has taken stay on v, v stays claimed): a goes on
+ *      with its next candidate.     6. otherwise return true.
+ *   list exhausted: action 4, claim p_a, return false.
+ * Properties:
+ *   - every agent is planned exactly once per step: N calls, at most 2N calls and returns;
+ *   - no edge collision arises, from any state.  A claim that stands is a move only if its
+ *     PLAN returned true, and true goes all the way up: nobody decided at that moment acts
+ *     otherwise later.  Of a swapping pair (a: p_a -> p_b, b: p_b -> p_a) let a's standing
+ *     claim be the earlier; b was then undecided, so it was the only undecided occupant
+ *     of p_b (two: rule 3), a pushed it, rule 2 barred p_a, and b is planned once;
+ *   - a node collision arises only among agents that shared a cell before the step.  Rule 1
+ *     gives a cell to one agent, except that an exhausted agent a claims p_a whoever holds
+ *     it.  A mover b into p_a claimed it while a was undecided -- then it pushed a (rule 3),
+ *     a returned false and b went on to another cell -- or while a, higher in the chain,
+ *     held another cell -- then a exhausts only after b returned false, i.e. b stays;
+ *   - the action depends on (seed, gid, t, a) and the env's state only: shard-invariant,
+ *     and two calls of T / 2 equal one of T.
+ * At eps_q = 2^32 this rule does NOT reproduce mapfx_action (descent does): a draw is
+ * dropped where ok_m fails or the cell is claimed, and a pushed agent does not draw.
+ * mapfx.rng.partial_policy_pibt_actions restates it and is its definition.
+ * Offered exactly where policy mode is (the wave kernel, u8 / int16 tables). */
+#define MAPFX_POLICY_DESCENT 0
+#define MAPFX_POLICY_PIBT 1
+/* MAPFX_EINVAL: a NULL handle, an unknown rule, or one not offered on this handle (the
+ * handle's rule is then unchanged). */
+int mapfx_partial_policy_rule(mapfx_partial_t* h, int32_t rule);
+/* 1: mapfx_partial_policy_rule(h, rule) succeeds; 0 otherwise. */
+int mapfx_partial_policy_rule_offered(const mapfx_partial_t* h, int32_t rule);
+
 /* T steps.  `actions` [T][E][N] of action_dtype, or NULL to use `pol`.  An action
  * outside 0..4 skips that env for that step only (env unchanged, reward 0.0, err set).
  * autoreset != 0: at the start of every step k (k = 0 included) an env whose terminated

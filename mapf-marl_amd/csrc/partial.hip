@@ -1045,6 +1045,98 @@ __device__ __forceinline__ int policy_action(const RArgs& ro, int env, int k, in
   return (pd >= 0 && best < pd) ? bm : 4;
 }
 
+// MAPFX_POLICY_PIBT (mapfx_partial.h; mapfx/rng.py partial_policy_pibt_actions is the rule's
+// definition): the env's agents are planned one at a time by its lane group, every lane of
+// the wave in the loop until the wave's last group is through -- no LDS, no barrier.
+//   per lane   dec / tgt / pact  decided, the cell it claims, its action: the claimed cells
+//                                are exactly the decided agents' tgt (a failed push leaves
+//                                the cell to the pushed agent, which stays on it)
+//              lst               the candidates it has not tried: 3 bits each, move + 1, 0 ends
+//              par / pcell       who pushed it and from where (the stack of the recursion:
+//                                an agent is planned once, so one entry per lane holds it)
+//   per group  ca                the agent being planned (the same value in the group's lanes)
+// One pass looks at one candidate of `ca`: the lane broadcasts (move, cell, parent) in one
+// word; two ballots masked to the group answer "claimed?" (decided lanes whose tgt is the
+// cell) and give U (undecided lanes standing on it) -- the agents' cells are the `cur`
+// registers.  A call (push) or a return changes ca; a return of true ends the whole chain.
+// At most 6 passes per agent (5 candidates and the exhausted list), 2 N calls and returns.
+// cur: the agent's index into the padded LDS map (one per cell), pitch: its row stride.
+// the cell offset of list entry m1 (move + 1): -pitch, +pitch, -1, +1, and 0 for stay (5)
+__device__ __forceinline__ int move_delta(int m1, int pitch) {
+  const int mag = m1 <= 2 ? pitch : 1;
+  return m1 == 5 ? 0 : (m1 & 1) ? -mag : mag;
+}
+__device__ __forceinline__ int pibt_action(const RArgs& ro, int N, int env, int k, int ag, bool has, int base,
+                                           uint64_t envmask, uint32_t avail, int pd, int d0, int d1, int d2,
+                                           int d3, int cur, int pitch) {
+  const uint32_t t = (uint32_t)(ro.t0 + k);
+  const uint64_t u = splitmix64(ro.seed ^ ((uint64_t)(ro.env_offset + env) * PK_ENV) ^ ((uint64_t)t * PK_T) ^
+                                ((uint64_t)(uint32_t)ag * PK_AGENT));
+  const bool explore = (u >> 32) < ro.eps_q;
+  // both candidate lists up front (every lane at once): the sorted one by ranks -- key
+  // d * 8 + m, stay as pd * 8 + 4, keys of moves that are not ok left out
+  constexpr int NOKEY = 0x7FFFFFFF;
+  uint32_t sorted = 5u, expl = 5u;  // pd < 0: stay alone
+  if (pd >= 0) {
+    const int key[5] = {(avail & 1u) && d0 >= 0 ? d0 * 8 : NOKEY, (avail & 2u) && d1 >= 0 ? d1 * 8 + 1 : NOKEY,
+                        (avail & 4u) && d2 >= 0 ? d2 * 8 + 2 : NOKEY, (avail & 8u) && d3 >= 0 ? d3 * 8 + 3 : NOKEY,
+                        pd * 8 + 4};
+    sorted = 0u;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+      int rank = 0;
+#pragma unroll
+      for (int j = 0; j < 5; ++j) rank += key[j] < key[i] ? 1 : 0;
+      if (key[i] != NOKEY) sorted |= (uint32_t)(i + 1) << (3 * rank);
+    }
+    const int m = (int)(u % 5ull);
+    const uint32_t okm = (key[0] != NOKEY ? 1u : 0u) | (key[1] != NOKEY ? 2u : 0u) | (key[2] != NOKEY ? 4u : 0u) |
+                         (key[3] != NOKEY ? 8u : 0u);
+    if ((okm >> m) & 1u) expl = (uint32_t)(m + 1) | (5u << 3);  // (m == 4: bit 4 is clear)
+  }
+  const uint32_t tm = t % (uint32_t)N;  // (a - t) mod N ascending: a = tm, tm + 1, .., N - 1, 0, .., tm - 1
+  bool dec = !has;
+  int tgt = -1, pact = 4, par = -1, pcell = -2;
+  uint32_t lst = 0u;
+  // the next agent planned at top level: undecided, off its goal first, then in rotated order
+  const auto select = [&]() {
+    const uint64_t und = (__ballot(has && !dec) & envmask) >> base;
+    const uint64_t off = (__ballot(has && !dec && pd != 0) & envmask) >> base;
+    const uint64_t c = off ? off : und;
+    const uint64_t hi = (c >> tm) << tm;
+    return c ? __ffsll((unsigned long long)(hi ? hi : c)) - 1 : -1;
+  };
+  int ca = select();
+  if (ag == ca) lst = explore ? expl : sorted;
+  while (__ballot(ca >= 0)) {
+    const bool on = ca >= 0, me = on && ag == ca;
+    const int m1 = (int)(lst & 7u);
+    const int v = m1 == 0 ? -1 : cur + move_delta(m1, pitch);
+    const uint32_t word = ((uint32_t)(v + 1) << 11) | (m1 != 0 && v == pcell ? 1024u : 0u) |
+                          ((uint32_t)(par + 1) << 3) | (uint32_t)m1;
+    const uint32_t wb = (uint32_t)__shfl((int)word, base + (on ? ca : 0));
+    const int mb = (int)(wb & 7u), parb = (int)((wb >> 3) & 127u) - 1, vb = (int)(wb >> 11) - 1;
+    const uint64_t cm = __ballot(on && has && dec && tgt == vb) & envmask;
+    const uint64_t um = __ballot(on && has && !dec && !me && mb != 5 && cur == vb) & envmask;
+    // (selects, no branches: the groups of a wave are at different places of their plans)
+    const bool exh = mb == 0;  // the list is exhausted: stay, false to the parent (or the chain ends)
+    const bool skip = !exh && ((cm != 0) | ((wb & 1024u) != 0) | (__popcll(um) >= 2));
+    const bool push = !exh && !skip && um != 0;  // the cell's occupant is planned next
+    const int child = __ffsll((unsigned long long)um) - 1 - base;  // (meaningful with push)
+    if (me && !skip) dec = true, pact = exh ? 4 : mb - 1, tgt = exh ? cur : vb;
+    if (me && !exh) lst >>= 3;  // (after a claim too: the next one, should the push fail)
+    if (push && ag == child) par = ca, pcell = cur - move_delta(mb, pitch), lst = sorted;
+    int nca = exh ? parb : skip ? ca : push ? child : -1;  // (-1: true, all the way up)
+    const int top = select();
+    if (on && nca < 0) {
+      nca = top;
+      if (ag == top) lst = explore ? expl : sorted;
+    }
+    ca = on ? nca : -1;
+  }
+  return pact;
+}
+
 // The body of partial_kernel (ROLL 0: one pass, exactly the step / observe / reset kernel)
 // and of partial_rollout_kernel (ROLL 1: T steps with the observation rows, ROLL 2: T steps
 // without them -- no feature rows, no K-nearest rows, no window planes, no staging).  The
@@ -1054,7 +1146,7 @@ __device__ __forceinline__ int policy_action(const RArgs& ro, int env, int k, in
 // (layout_rollout) keeps the staging images clear of live data, so nothing is rebuilt
 // between steps; stale low bits of dep are harmless: every occupant of a cell writes its
 // move before anyone reads it.
-template <int WIN, int KF, int LF, int GDE, bool RUN, int ROLL>
+template <int WIN, int KF, int LF, int GDE, bool RUN, int ROLL, int RULE = MAPFX_POLICY_DESCENT>
 __device__ __forceinline__ void partial_body(const PGeo& g_, const PArgs& a_, const RArgs& ro, const RRun& rn,
                                              const int blk) {
   std::conditional_t<ROLL != 0, PArgs, const PArgs&> a = a_;  // (the rollout advances the outputs)
@@ -1377,7 +1469,10 @@ __device__ __forceinline__ void partial_body(const PGeo& g_, const PArgs& a_, co
       if (map[cur + pitch]) pm |= 2u;
       if (map[cur - 1]) pm |= 4u;
       if (map[cur + 1]) pm |= 8u;
-      act = has ? policy_action(ro, env, k, ag, pm, pd, nbd0, nbd1, nbd2, nbd3) : 4;
+      if constexpr (RULE == MAPFX_POLICY_PIBT)  // (every lane of the wave: the plan runs on ballots)
+        act = pibt_action(ro, N, env, k, ag, has, base, envmask, pm, pd, nbd0, nbd1, nbd2, nbd3, cur, pitch);
+      else
+        act = has ? policy_action(ro, env, k, ag, pm, pd, nbd0, nbd1, nbd2, nbd3) : 4;
       if (has && ro.actions) ro.actions[(long long)k * g.E * N + oa] = (int8_t)act;
     } else if (k > 0) {
       act = has ? decode_raw(araw_n, abyte_n) : 4;
@@ -1925,6 +2020,18 @@ __global__ void __launch_bounds__(64 * PARTIAL_MAX_WPB) partial_runner_rollout_k
   partial_body<WIN, KF, LF, GDE, true, OBS ? 1 : 2>(g_, a, ro, rn, (int)blockIdx.x);
 }
 
+// The two rollout kernels with the policy rule MAPFX_POLICY_PIBT (policy mode only): instances
+// of their own, so the descent instances keep their code and their registers.
+template <int WIN, int KF, int LF, int GDE, bool OBS>
+__global__ void __launch_bounds__(64 * PARTIAL_MAX_WPB) partial_pibt_rollout_kernel(PGeo g_, PArgs a, RArgs ro) {
+  partial_body<WIN, KF, LF, GDE, false, OBS ? 1 : 2, MAPFX_POLICY_PIBT>(g_, a, ro, RRun{}, (int)blockIdx.x);
+}
+template <int WIN, int KF, int LF, int GDE, bool OBS>
+__global__ void __launch_bounds__(64 * PARTIAL_MAX_WPB) partial_pibt_runner_rollout_kernel(PGeo g_, PArgs a,
+                                                                                           RArgs ro, RRun rn) {
+  partial_body<WIN, KF, LF, GDE, true, OBS ? 1 : 2, MAPFX_POLICY_PIBT>(g_, a, ro, rn, (int)blockIdx.x);
+}
+
 // A goal-table rebuild makes the carried distances stale: pdist of every (masked) env
 // becomes PD_NONE, so its next step looks the current and target cells up in the new
 // table (marl_partial.py:228-229 reads _goal_dist afresh every step); pnbr is only read
@@ -2061,6 +2168,7 @@ struct mapfx_partial_t {
   int device;
   int no_nbcarry;  // diagnostic builds (MAPFX_PARTIAL_DIAG_ENV) only: ignore the state's pnbr
   int32_t* err;    // mapfx_partial_bind_err: where the calls without a mapfx_partial_out report
+  int32_t rule;    // mapfx_partial_policy_rule: MAPFX_POLICY_* of the next policy-mode launch
 };
 
 namespace {
@@ -2132,66 +2240,89 @@ PartialFn pick(int win, int K, int L, int tw, bool run) {
 // fast ones, the six generic windows); without them the window and K play no part: one per
 // fast lane group and table width, and one generic.
 using RolloutFn = void (*)(PGeo, PArgs, RArgs);
-template <int WIN, int LF, bool OBS>
-RolloutFn pick_roll_fast(int tw) {
-  return tw == 1 ? partial_rollout_kernel<WIN, 5, LF, 1, OBS> : tw == 2 ? partial_rollout_kernel<WIN, 5, LF, 2, OBS>
-                                                                        : partial_rollout_kernel<WIN, 5, LF, 0, OBS>;
+// (RULE: MAPFX_POLICY_PIBT has instances of its own -- partial_pibt_rollout_kernel -- of the
+// shapes policy mode is offered on: none for int32 tables alone)
+template <int RULE, int WIN, int KF, int LF, int GDE, bool OBS>
+RolloutFn roll_inst() {
+  if constexpr (RULE == MAPFX_POLICY_PIBT) return partial_pibt_rollout_kernel<WIN, KF, LF, GDE, OBS>;
+  else return partial_rollout_kernel<WIN, KF, LF, GDE, OBS>;
 }
+template <int RULE, int WIN, int LF, bool OBS>
+RolloutFn pick_roll_fast(int tw) {
+  if (tw == 1) return roll_inst<RULE, WIN, 5, LF, 1, OBS>();
+  if (tw == 2) return roll_inst<RULE, WIN, 5, LF, 2, OBS>();
+  if constexpr (RULE == MAPFX_POLICY_PIBT) return nullptr;
+  else return roll_inst<RULE, WIN, 5, LF, 0, OBS>();
+}
+template <int RULE = MAPFX_POLICY_DESCENT>
 RolloutFn pick_roll(int win, int K, int L, int tw, bool obs) {
   if (!obs) {
-    if (L == 8) return pick_roll_fast<0, 8, false>(tw);
-    if (L == 16) return pick_roll_fast<0, 16, false>(tw);
-    if (L == 32) return pick_roll_fast<0, 32, false>(tw);
-    return partial_rollout_kernel<0, 0, 0, 0, false>;
+    if (L == 8) return pick_roll_fast<RULE, 0, 8, false>(tw);
+    if (L == 16) return pick_roll_fast<RULE, 0, 16, false>(tw);
+    if (L == 32) return pick_roll_fast<RULE, 0, 32, false>(tw);
+    return roll_inst<RULE, 0, 0, 0, 0, false>();
   }
-  if (K == 5 && win == 5 && L == 16) return pick_roll_fast<5, 16, true>(tw);
-  if (K == 5 && win == 5 && L == 8) return pick_roll_fast<5, 8, true>(tw);
-  if (K == 5 && win == 5 && L == 32) return pick_roll_fast<5, 32, true>(tw);
-  if (K == 5 && win == 3 && L == 16) return pick_roll_fast<3, 16, true>(tw);
-  if (K == 5 && win == 7 && L == 16) return pick_roll_fast<7, 16, true>(tw);
+  if (K == 5 && win == 5 && L == 16) return pick_roll_fast<RULE, 5, 16, true>(tw);
+  if (K == 5 && win == 5 && L == 8) return pick_roll_fast<RULE, 5, 8, true>(tw);
+  if (K == 5 && win == 5 && L == 32) return pick_roll_fast<RULE, 5, 32, true>(tw);
+  if (K == 5 && win == 3 && L == 16) return pick_roll_fast<RULE, 3, 16, true>(tw);
+  if (K == 5 && win == 7 && L == 16) return pick_roll_fast<RULE, 7, 16, true>(tw);
   switch (win) {
-    case 0: return partial_rollout_kernel<0, 0, 0, 0, true>;
-    case 1: return partial_rollout_kernel<1, 0, 0, 0, true>;
-    case 3: return partial_rollout_kernel<3, 0, 0, 0, true>;
-    case 5: return partial_rollout_kernel<5, 0, 0, 0, true>;
-    case 7: return partial_rollout_kernel<7, 0, 0, 0, true>;
-    case 9: return partial_rollout_kernel<9, 0, 0, 0, true>;
+    case 0: return roll_inst<RULE, 0, 0, 0, 0, true>();
+    case 1: return roll_inst<RULE, 1, 0, 0, 0, true>();
+    case 3: return roll_inst<RULE, 3, 0, 0, 0, true>();
+    case 5: return roll_inst<RULE, 5, 0, 0, 0, true>();
+    case 7: return roll_inst<RULE, 7, 0, 0, 0, true>();
+    case 9: return roll_inst<RULE, 9, 0, 0, 0, true>();
   }
   return nullptr;
+}
+RolloutFn pick_roll_rule(int rule, int win, int K, int L, int tw, bool obs) {
+  return rule == MAPFX_POLICY_PIBT ? pick_roll<MAPFX_POLICY_PIBT>(win, K, L, tw, obs) : pick_roll(win, K, L, tw, obs);
 }
 
 // partial_runner_rollout_kernel's instances: with the rows the five fast shapes of the
 // runner's step at u8 / int16 tables and the six generic windows (which also take the fast
 // shapes' int32 tables); without the rows one per fast lane group (table width at run time)
-// and one generic.
+// and one generic.  RULE as above (partial_pibt_runner_rollout_kernel).
 using RunRollFn = void (*)(PGeo, PArgs, RArgs, RRun);
-template <int WIN, int LF>
-RunRollFn pick_run_roll_fast(int tw) {
-  return tw == 1 ? partial_runner_rollout_kernel<WIN, 5, LF, 1, true> : partial_runner_rollout_kernel<WIN, 5, LF, 2, true>;
+template <int RULE, int WIN, int KF, int LF, int GDE, bool OBS>
+RunRollFn run_roll_inst() {
+  if constexpr (RULE == MAPFX_POLICY_PIBT) return partial_pibt_runner_rollout_kernel<WIN, KF, LF, GDE, OBS>;
+  else return partial_runner_rollout_kernel<WIN, KF, LF, GDE, OBS>;
 }
+template <int RULE, int WIN, int LF>
+RunRollFn pick_run_roll_fast(int tw) {
+  return tw == 1 ? run_roll_inst<RULE, WIN, 5, LF, 1, true>() : run_roll_inst<RULE, WIN, 5, LF, 2, true>();
+}
+template <int RULE = MAPFX_POLICY_DESCENT>
 RunRollFn pick_run_roll(int win, int K, int L, int tw, bool obs) {
   if (!obs) {
-    if (L == 8) return partial_runner_rollout_kernel<0, 5, 8, 0, false>;
-    if (L == 16) return partial_runner_rollout_kernel<0, 5, 16, 0, false>;
-    if (L == 32) return partial_runner_rollout_kernel<0, 5, 32, 0, false>;
-    return partial_runner_rollout_kernel<0, 0, 0, 0, false>;
+    if (L == 8) return run_roll_inst<RULE, 0, 5, 8, 0, false>();
+    if (L == 16) return run_roll_inst<RULE, 0, 5, 16, 0, false>();
+    if (L == 32) return run_roll_inst<RULE, 0, 5, 32, 0, false>();
+    return run_roll_inst<RULE, 0, 0, 0, 0, false>();
   }
   if (tw != 0) {
-    if (K == 5 && win == 5 && L == 16) return pick_run_roll_fast<5, 16>(tw);
-    if (K == 5 && win == 5 && L == 8) return pick_run_roll_fast<5, 8>(tw);
-    if (K == 5 && win == 5 && L == 32) return pick_run_roll_fast<5, 32>(tw);
-    if (K == 5 && win == 3 && L == 16) return pick_run_roll_fast<3, 16>(tw);
-    if (K == 5 && win == 7 && L == 16) return pick_run_roll_fast<7, 16>(tw);
+    if (K == 5 && win == 5 && L == 16) return pick_run_roll_fast<RULE, 5, 16>(tw);
+    if (K == 5 && win == 5 && L == 8) return pick_run_roll_fast<RULE, 5, 8>(tw);
+    if (K == 5 && win == 5 && L == 32) return pick_run_roll_fast<RULE, 5, 32>(tw);
+    if (K == 5 && win == 3 && L == 16) return pick_run_roll_fast<RULE, 3, 16>(tw);
+    if (K == 5 && win == 7 && L == 16) return pick_run_roll_fast<RULE, 7, 16>(tw);
   }
   switch (win) {
-    case 0: return partial_runner_rollout_kernel<0, 0, 0, 0, true>;
-    case 1: return partial_runner_rollout_kernel<1, 0, 0, 0, true>;
-    case 3: return partial_runner_rollout_kernel<3, 0, 0, 0, true>;
-    case 5: return partial_runner_rollout_kernel<5, 0, 0, 0, true>;
-    case 7: return partial_runner_rollout_kernel<7, 0, 0, 0, true>;
-    case 9: return partial_runner_rollout_kernel<9, 0, 0, 0, true>;
+    case 0: return run_roll_inst<RULE, 0, 0, 0, 0, true>();
+    case 1: return run_roll_inst<RULE, 1, 0, 0, 0, true>();
+    case 3: return run_roll_inst<RULE, 3, 0, 0, 0, true>();
+    case 5: return run_roll_inst<RULE, 5, 0, 0, 0, true>();
+    case 7: return run_roll_inst<RULE, 7, 0, 0, 0, true>();
+    case 9: return run_roll_inst<RULE, 9, 0, 0, 0, true>();
   }
   return nullptr;
+}
+RunRollFn pick_run_roll_rule(int rule, int win, int K, int L, int tw, bool obs) {
+  return rule == MAPFX_POLICY_PIBT ? pick_run_roll<MAPFX_POLICY_PIBT>(win, K, L, tw, obs)
+                                   : pick_run_roll(win, K, L, tw, obs);
 }
 
 // The rollout's layout of a wave-kernel configuration: layout()'s regions, with the staging
@@ -2460,15 +2591,17 @@ int mapfx_partial_create(const mapfx_partial_cfg* cfg, mapfx_partial_t** out) {
                              "hipFuncSetAttribute(partial_kernel LDS)");
   }
   if (!g.big) {  // the rollout's two layouts and this configuration's two instances
-    for (int obs = 0; obs < 2 && !rc; ++obs) {
+    for (int i = 0; i < 4 && !rc; ++i) {  // (i >> 1: the policy rule, pibt where it is offered)
+      const int obs = i & 1, rule = i >> 1;
+      if (rule != MAPFX_POLICY_DESCENT && g.gd32) break;
       PGeo& gr = h->geo_roll[obs];
-      layout_rollout(g, obs != 0, gr);
-      const RolloutFn fn = pick_roll(g.win, g.K, g.L, g.gd8 ? 1 : g.gd32 ? 0 : 2, obs != 0);
+      if (rule == MAPFX_POLICY_DESCENT) layout_rollout(g, obs != 0, gr);
+      const RolloutFn fn = pick_roll_rule(rule, g.win, g.K, g.L, g.gd8 ? 1 : g.gd32 ? 0 : 2, obs != 0);
       if (fn && gr.lds * gr.wpb > 64 * 1024)
         rc = check_hip(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize,
                                            gr.lds * gr.wpb),
                        "hipFuncSetAttribute(partial_rollout_kernel LDS)");
-      const RunRollFn rfn = pick_run_roll(g.win, g.K, g.L, g.gd8 ? 1 : g.gd32 ? 0 : 2, obs != 0);
+      const RunRollFn rfn = pick_run_roll_rule(rule, g.win, g.K, g.L, g.gd8 ? 1 : g.gd32 ? 0 : 2, obs != 0);
       if (!rc && rfn && gr.lds * gr.wpb > 64 * 1024)
         rc = check_hip(hipFuncSetAttribute((const void*)rfn, hipFuncAttributeMaxDynamicSharedMemorySize,
                                            gr.lds * gr.wpb),
@@ -2737,7 +2870,8 @@ int mapfx_partial_rollout(mapfx_partial_t* h, const mapfx_partial_state* st, int
     return rc;
   }
   const bool obs = tj.obs != nullptr;
-  const RolloutFn fn = pick_roll(g.win, g.K, g.L, g.gd8 ? 1 : g.gd32 ? 0 : 2, obs);
+  const RolloutFn fn = pick_roll_rule(policy ? h->rule : MAPFX_POLICY_DESCENT, g.win, g.K, g.L,
+                                      g.gd8 ? 1 : g.gd32 ? 0 : 2, obs);
   if (!fn) return perr(MAPFX_EINVAL, "obs_window must be one of 0, 1, 3, 5, 7, 9");
   a.bonus_lut = h->bonus_lut;
   if (h->no_nbcarry) a.pnbr = nullptr;
@@ -2774,6 +2908,24 @@ int mapfx_partial_bind_err(mapfx_partial_t* h, int32_t* err) {
   return MAPFX_OK;
 }
 
+int mapfx_partial_policy_rule_offered(const mapfx_partial_t* h, int32_t rule) {
+  if (!h) return 0;
+  if (rule == MAPFX_POLICY_DESCENT) return 1;
+  return rule == MAPFX_POLICY_PIBT && !h->geo.big && !h->geo.gd32 ? 1 : 0;
+}
+
+int mapfx_partial_policy_rule(mapfx_partial_t* h, int32_t rule) {
+  if (!h) return perr(MAPFX_EINVAL, "NULL handle");
+  if (rule != MAPFX_POLICY_DESCENT && rule != MAPFX_POLICY_PIBT)
+    return perr(MAPFX_EINVAL, "mapfx_partial_policy_rule: unknown rule");
+  if (!mapfx_partial_policy_rule_offered(h, rule))
+    return perr(MAPFX_EINVAL,
+                "mapfx_partial_policy_rule: MAPFX_POLICY_PIBT needs the wave kernel (N <= 64, sides <= 256) "
+                "and u8 / int16 goal tables (H * W <= 32767)");
+  h->rule = rule;
+  return MAPFX_OK;
+}
+
 int mapfx_partial_runner_rollout_offered(const mapfx_partial_t* h, int policy) {
   return h && !h->geo.big && !(policy && h->geo.gd32) ? 1 : 0;
 }
@@ -2799,7 +2951,8 @@ int mapfx_partial_rollout_runner(mapfx_partial_t* h, const mapfx_partial_state* 
                        : "mapfx_runner_rollout: offered on the wave kernel only (N <= 64, sides <= 256)");
   if (g.E == 0) return MAPFX_OK;
   const bool obs = rr->obs_rows != nullptr;
-  const RunRollFn fn = pick_run_roll(g.win, g.K, g.L, g.gd8 ? 1 : g.gd32 ? 0 : 2, obs);
+  const RunRollFn fn = pick_run_roll_rule(policy ? h->rule : MAPFX_POLICY_DESCENT, g.win, g.K, g.L,
+                                          g.gd8 ? 1 : g.gd32 ? 0 : 2, obs);
   if (!fn) return perr(MAPFX_EINVAL, "obs_window must be one of 0, 1, 3, 5, 7, 9");
   PArgs a;
   memset(&a, 0, sizeof(a));

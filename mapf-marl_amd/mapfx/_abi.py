@@ -20,6 +20,8 @@ MAPFX_OBS_FULL = 1
 MAPFX_OBS_WINDOW = 2
 MAPFX_OBS_PRIMAL = 4
 MAPFX_I8, MAPFX_I32, MAPFX_I64 = 0, 1, 2
+# include/mapfx_partial.h MAPFX_POLICY_*: the on-device policy's rules by their Python names
+POLICY_RULES = {"descent": 0, "pibt": 1}
 
 c_i32, c_i64, c_u64, c_f64, c_vp = (ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64,
                                     ctypes.c_double, ctypes.c_void_p)
@@ -123,7 +125,8 @@ EXPORTS = ("mapfx_abi_version", "mapfx_last_error", "mapfx_build_id", "mapfx_las
            "mapfx_primal_blocking_count",
            "mapfx_primal_blocking", "mapfx_primal_generate", "mapfx_runner_begin", "mapfx_runner_actions", "mapfx_runner_post",
            "mapfx_runner_step", "mapfx_host_ring_alloc", "mapfx_host_ring_free",
-           "mapfx_partial_bind_err", "mapfx_runner_rollout", "mapfx_runner_rollout_offered")
+           "mapfx_partial_bind_err", "mapfx_runner_rollout", "mapfx_runner_rollout_offered",
+           "mapfx_partial_policy_rule", "mapfx_partial_policy_rule_offered")
 
 
 class ERows(ctypes.Structure):  # include/mapfx_runner.h mapfx_episode_rows
@@ -200,6 +203,8 @@ def _load():
         "mapfx_runner_step": (c_i32, [c_vp, P(PState), P(POut), P(RState), c_vp, c_i32, c_i64, c_i32,
                                       c_vp, P(ERows), c_vp]),
         "mapfx_partial_bind_err": (c_i32, [c_vp, c_vp]),
+        "mapfx_partial_policy_rule": (c_i32, [c_vp, c_i32]),
+        "mapfx_partial_policy_rule_offered": (c_i32, [c_vp, c_i32]),
         "mapfx_runner_rollout": (c_i32, [c_vp, P(PState), P(RState), c_i32, c_i32, c_vp, c_i32,
                                          P(PPolicy), c_vp, P(ERows), c_vp]),
         "mapfx_runner_rollout_offered": (c_i32, [c_vp, c_i32]),

@@ -194,20 +194,41 @@ class MarlPartialBatch(DeviceBatch):
             spec["actions"] = ((T, E, N), torch.int8)
         return spec
 
+    def policy_rule_offered(self, policy):
+        """True where the on-device policy rule `policy` ("descent" / "pibt") can be used."""
+        rule = _abi.POLICY_RULES.get(policy)
+        return rule is not None and bool(lib.mapfx_partial_policy_rule_offered(self._h, rule))
+
+    def set_policy_rule(self, policy):
+        """The rule of the next policy-mode launches of this batch (mapfx_partial_policy_rule):
+        "descent" or "pibt".  ValueError for an unknown rule or one not offered here (pibt:
+        n_agents <= 64, sides <= 256 and H * W <= 32767)."""
+        if policy not in _abi.POLICY_RULES:
+            raise ValueError("policy must be one of %s, not %r" % (sorted(_abi.POLICY_RULES), policy))
+        if not self.policy_rule_offered(policy):
+            raise ValueError("policy %r is not offered for n_agents = %d on a %d x %d map (it needs "
+                             "n_agents <= 64, sides <= 256 and H * W <= 32767)"
+                             % (policy, self.N, self.H, self.W))
+        check(lib.mapfx_partial_policy_rule(self._h, _abi.POLICY_RULES[policy]), "mapfx_partial_policy_rule")
+
     def rollout(self, actions=None, T=None, *, eps=None, seed=0, t0=0, autoreset=False, obs=True,
-                out=None):
+                out=None, policy="descent"):
         """T steps in one call (mapfx_partial_rollout; one launch where `rollout_fused()`).
 
         actions: [T, E, N] int8 / int32 / int64 -- or actions=None with T and eps (a float in
         0..1, mapped to eps_q = round(eps * 2**32), or an int eps_q in 0..2**32): the
         on-device policy (rng.partial_policy_actions: shortest-path descent with eps-random
-        moves keyed by (seed, global env, t0 + k, agent)).  autoreset: an env whose
+        moves keyed by (seed, global env, t0 + k, agent)) -- or, with policy="pibt", the
+        collision-free rule rng.partial_policy_pibt_actions (priority inheritance with
+        backtracking; the same eps and keys).  The rule is set per call; ValueError where it
+        is not offered.  autoreset: an env whose
         terminated flag is set restarts from init_pos before it is stepped.  Returns a dict
         of trajectory tensors whose slot k is what the k-th of T `step` calls returns --
         reward [T, E], obs [T, E, N, D] (absent and not built with obs=False), state, avail,
         pos and terminated after that step, actions in policy mode -- allocated once per
         (T, obs, mode) and reused, or the caller's own `out` (the same keys; a missing one
         is not produced)."""
+        self.set_policy_rule(policy)
         policy = actions is None
         if policy:
             if T is None or eps is None:

@@ -84,6 +84,103 @@ def partial_policy_actions(seed, env_ids, t, eps_q, avail, pd, d):
     return np.where(explore, (u % np.uint64(5)).astype(np.int64), greedy).astype(np.int8)
 
 
+PIBT_STEPS = ((-1, 0), (1, 0), (0, -1), (0, 1))      # move 0 up, 1 down, 2 left, 3 right
+# what partial_policy_pibt_actions(stats=True) counts, in this order
+PIBT_STATS = ("push", "push_failed", "depth3", "skip_claimed", "skip_parent", "skip_multi",
+              "explore_top", "explore_pushed", "forced_stay")
+
+
+def partial_policy_pibt_actions(seed, env_ids, t, eps_q, avail, pd, d, pos, stats=False):
+    """The collision-free on-device policy (MAPFX_POLICY_PIBT of include/mapfx_partial.h:
+    one-step priority inheritance with backtracking), restated for one step.  This function
+    is the rule's definition.
+
+    u, explore = (u >> 32) < eps_q and ok_m = bit m of the PRE-step avail mask and d[m] >= 0
+    are `partial_policy_actions`' own.  Candidates of agent a, as (move, cell):
+      pd < 0                         stay alone
+      called at top level, explore   [u % 5 if it is a move m < 4 with ok_m], then stay
+      otherwise (a pushed agent too) the ok_m moves and stay as (pd, 4), ascending by (d, m)
+    Agents are planned in ascending (pd == 0, (a - t) mod N), t as an unsigned 32-bit value;
+    one still undecided at its turn runs PLAN(a, none).  PLAN(a, parent), per candidate
+    (m, v) in order: skip v when it is claimed; when it is the parent's cell (no swap); when
+    m != 4 and two or more undecided agents other than a stand on v.  Else claim v and decide
+    a with m; a single undecided occupant b of v runs PLAN(b, a), and when that returns
+    False (b stays on v, which stays claimed) a goes on with its next candidate; otherwise
+    return True.  A list exhausted: a stays (4), claims its own cell, returns False.
+
+    pos [E, N, 2] the agents' (row, col); the other arguments as `partial_policy_actions`.
+    Returns int8 [E, N]; with stats=True also an int64 [len(PIBT_STATS)] of branch counts.
+    """
+    avail = np.asarray(avail, dtype=np.int64)
+    pd = np.asarray(pd, dtype=np.int64)
+    d = np.asarray(d, dtype=np.int64)
+    pos = np.asarray(pos, dtype=np.int64)
+    E, N = pd.shape
+    env = np.asarray(env_ids, dtype=np.int64).astype(np.uint64)[:, None]
+    ag = np.arange(N, dtype=np.uint64)[None, :]
+    tt = int(t) & 0xFFFFFFFF
+    u = splitmix64(np.uint64(seed) ^ _mul(env, K_ENV) ^ _mul(np.uint64(tt), K_T) ^ _mul(ag, K_AGENT))
+    explore = (u >> np.uint64(32)) < np.uint64(eps_q)
+    draw = (u % np.uint64(5)).astype(np.int64)
+    ok = (((avail[..., None] >> np.arange(4)) & 1) == 1) & (d >= 0)
+    acts = np.full((E, N), 4, dtype=np.int8)
+    cnt = dict.fromkeys(PIBT_STATS, 0)
+    for e in range(E):
+        cell = [(int(pos[e, a, 0]), int(pos[e, a, 1])) for a in range(N)]
+        decided = [False] * N
+        claimed = set()
+
+        def candidates(a, top):
+            stay = (4, cell[a])
+            if pd[e, a] < 0:
+                return [stay]
+            if explore[e, a]:
+                cnt["explore_top" if top else "explore_pushed"] += 1
+            if top and explore[e, a]:
+                m = int(draw[e, a])
+                return ([(m, (cell[a][0] + PIBT_STEPS[m][0], cell[a][1] + PIBT_STEPS[m][1]))]
+                        if m < 4 and ok[e, a, m] else []) + [stay]
+            keys = sorted([(int(d[e, a, m]), m) for m in range(4) if ok[e, a, m]] + [(int(pd[e, a]), 4)])
+            return [(m, cell[a] if m == 4 else (cell[a][0] + PIBT_STEPS[m][0], cell[a][1] + PIBT_STEPS[m][1]))
+                    for _, m in keys]
+
+        def plan(a, parent, depth):
+            if depth >= 3:
+                cnt["depth3"] += 1
+            for m, v in candidates(a, parent is None):
+                if v in claimed:
+                    cnt["skip_claimed"] += 1
+                    continue
+                if parent is not None and v == cell[parent]:
+                    cnt["skip_parent"] += 1
+                    continue
+                occ = [b for b in range(N) if b != a and not decided[b] and cell[b] == v] if m != 4 else []
+                if len(occ) >= 2:
+                    cnt["skip_multi"] += 1
+                    continue
+                claimed.add(v)
+                decided[a] = True
+                acts[e, a] = m
+                if occ:
+                    cnt["push"] += 1
+                    if not plan(occ[0], a, depth + 1):
+                        cnt["push_failed"] += 1
+                        continue
+                return True
+            cnt["forced_stay"] += 1
+            decided[a] = True
+            acts[e, a] = 4
+            claimed.add(cell[a])
+            return False
+
+        for a in sorted(range(N), key=lambda a: (bool(pd[e, a] == 0), (a - tt) % N)):
+            if not decided[a]:
+                plan(a, None, 1)
+    if stats:
+        return acts, np.array([cnt[k] for k in PIBT_STATS], dtype=np.int64)
+    return acts
+
+
 def runner_policy_seed(seed, run):
     """The policy seed of run number `run` of ParallelRunner.collect:
     splitmix64(seed ^ run * K_T) -- a pure function of (seed, run), so every run draws its

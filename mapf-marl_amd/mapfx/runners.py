@@ -331,19 +331,22 @@ class ParallelRunner:
         self.t = k
         return self._finish(test_mode)
 
-    def collect(self, eps=0.0, seed=None, actions=None, test_mode=False, chunk=None):
+    def collect(self, eps=0.0, seed=None, actions=None, test_mode=False, chunk=None, policy="descent"):
         """One run with no MAC: the episode loop as one launch (mapfx_runner_rollout), the
         actions from the on-device policy -- each agent descends its shortest path, a
         fraction `eps` of the moves uniform random (eps_q = round(eps * 2**32): eps=1.0 is
         PyMARL's initial epsilon, eps=0.0 the shortest-path baseline; rng.partial_policy_actions
         restates it, keyed by rng.runner_policy_seed(seed, run number), seed=None: args.seed)
-        -- or from `actions`, a [max_t, B, N] int8 / int32 / int64 device tensor indexed by
+        ; policy="pibt": the collision-free rule rng.partial_policy_pibt_actions instead of
+        the descent, same eps and keys, ValueError where it is not offered --
+        or from `actions`, a [max_t, B, N] int8 / int32 / int64 device tensor indexed by
         env.  The EpisodeBatch, t_env, the returns and the logged stats are those of `run()`
         with a MAC that returns the same actions.  chunk: steps per call (None: all max_t
         in one; a tuple: the successive call lengths).  Nothing is read on the host before
         the run's totals.  ValueError where the fused call is not offered (N > 64 or a side
         > 256; the policy also needs H * W <= 32767): use run() with a MAC there."""
         env = self.env
+        env.set_policy_rule(policy)
         policy = actions is None
         if not lib.mapfx_runner_rollout_offered(env._h, 1 if policy else 0):
             raise ValueError(

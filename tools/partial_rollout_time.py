@@ -12,6 +12,11 @@ launches:
   fused_noobs   (b) ... obs=False
   policy_eps0   (c) ... the on-device policy, eps_q = 0, obs=False
   policy_eps1   (c) ... eps_q = 2**32, obs=False
+  pibt_eps0     (d) (c) under policy="pibt" (priority inheritance with backtracking), eps_q = 0
+  pibt_eps005   (d) ... eps 0.05
+  pibt_eps1     (d) ... eps_q = 2**32
+The policy legs also report what their episodes came to after [reset, T steps]: the share of
+envs with every agent on its goal and the device's total_coll per env.
 
 Timing: stream events around enough replays of a leg's graph to fill --window seconds
 (calibrated per leg after its warm-up), --reps alternations over all legs in one session;
@@ -20,7 +25,8 @@ step are algorithmic, from shapes (rollout_bytes_per_env_step below; the loop le
 bench.py's partial_bytes_per_env_step), and their share of the 8 TB/s roofline follows.
 `separated`: every repeat of fused_noobs below every repeat of loop_noobs at that T.
 
-  python tools/partial_rollout_time.py [--window 1.0] [--reps 5] [--out profiles/partial_rollout_time.json]
+  python tools/partial_rollout_time.py [--window 1.0] [--reps 5] [--T 64] [--legs policy_eps0 pibt_eps0]
+                                        [--out profiles/partial_rollout_time.json]
 """
 import argparse
 import ctypes
@@ -36,7 +42,8 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 HBM_BYTES_PER_S = 8e12
-LEGS = ("loop_obs", "loop_noobs", "fused_obs", "fused_noobs", "policy_eps0", "policy_eps1")
+ALL_LEGS = ("loop_obs", "loop_noobs", "fused_obs", "fused_noobs", "policy_eps0", "policy_eps1", "pibt_eps0",
+            "pibt_eps005", "pibt_eps1")
 
 
 def rollout_bytes_per_env_step(N, D, HW, gd_bytes, T, obs, policy):
@@ -57,8 +64,10 @@ def main():
     ap.add_argument("--window", type=float, default=1.0, help="seconds per timed window")
     ap.add_argument("--reps", type=int, default=5, help="alternations over all legs")
     ap.add_argument("--T", type=int, nargs="+", default=[1, 8, 32, 64])
+    ap.add_argument("--legs", nargs="+", default=list(ALL_LEGS), choices=ALL_LEGS)
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "partial_rollout_time.json"))
     a = ap.parse_args()
+    LEGS = tuple(leg for leg in ALL_LEGS if leg in a.legs)
     if not torch.cuda.is_available():
         raise SystemExit("partial_rollout_time needs a HIP device")
     import bench
@@ -97,8 +106,9 @@ def main():
             return lambda: b.rollout(acts[:T])
         if leg == "fused_noobs":
             return lambda: b.rollout(acts[:T], obs=False)
-        eps_q = 0 if leg == "policy_eps0" else 2 ** 32
-        return lambda: b.rollout(T=T, eps=eps_q, seed=3, obs=False)
+        eps_q = 0 if leg.endswith("eps0") else int(round(0.05 * 2 ** 32)) if leg.endswith("eps005") else 2 ** 32
+        rule = "pibt" if leg.startswith("pibt") else "descent"
+        return lambda: b.rollout(T=T, eps=eps_q, seed=3, obs=False, policy=rule)
 
     D = None
     results = {}
@@ -124,7 +134,7 @@ def main():
                 g.replay()
             torch.cuda.synchronize()
             graphs[leg], batches[leg] = g, b
-        if T == min(8, Tmax):   # faster and different is not faster: the legs agree
+        if T == min(8, Tmax) and set(ALL_LEGS[:4]) <= set(LEGS):   # faster and different is not faster: the legs agree
             ref = batches["loop_obs"]
             for leg in ("loop_noobs", "fused_obs", "fused_noobs"):
                 for f in ("pos", "t", "total_coll", "pdist"):
@@ -144,13 +154,16 @@ def main():
         for _ in range(a.reps):                 # alternate over the legs
             for leg in LEGS:
                 ms[leg].append(timed(graphs[leg], replays[leg]) / (replays[leg] * T) * 1e3)
-        gd = batches["loop_obs"].goal_dist.element_size()
+        gd = batches[LEGS[0]].goal_dist.element_size()
         full = bench.partial_bytes_per_env_step(N, D, S * S, gd)
         by = {"loop_obs": full, "loop_noobs": full - 4 * D * N,
               "fused_obs": rollout_bytes_per_env_step(N, D, S * S, gd, T, True, False),
               "fused_noobs": rollout_bytes_per_env_step(N, D, S * S, gd, T, False, False),
               "policy_eps0": rollout_bytes_per_env_step(N, D, S * S, gd, T, False, True),
-              "policy_eps1": rollout_bytes_per_env_step(N, D, S * S, gd, T, False, True)}
+              "policy_eps1": rollout_bytes_per_env_step(N, D, S * S, gd, T, False, True),
+              "pibt_eps0": rollout_bytes_per_env_step(N, D, S * S, gd, T, False, True),
+              "pibt_eps005": rollout_bytes_per_env_step(N, D, S * S, gd, T, False, True),
+              "pibt_eps1": rollout_bytes_per_env_step(N, D, S * S, gd, T, False, True)}
         res = {}
         for leg in LEGS:
             lo, hi = min(ms[leg]), max(ms[leg])
@@ -158,7 +171,12 @@ def main():
                         "replays_per_window": replays[leg], "kernel": kernels[leg],
                         "bytes_per_step": round(E * by[leg], 1),
                         "roofline_share_at_min": round(E * by[leg] / (lo * 1e-3) / HBM_BYTES_PER_S, 5)}
-        res["separated"] = max(ms["fused_noobs"]) < min(ms["loop_noobs"])
+            if leg in ALL_LEGS[4:]:     # the state the last replay left: [reset, T policy steps]
+                bt = batches[leg]
+                res[leg]["completed_share"] = round(float(bt.at_goal.bool().all(1).float().mean().item()), 4)
+                res[leg]["collisions_per_env"] = round(float(bt.total_coll.float().mean().item()), 3)
+        res["separated"] = ("fused_noobs" in ms and "loop_noobs" in ms and
+                            max(ms["fused_noobs"]) < min(ms["loop_noobs"]))
         results[str(T)] = res
         del graphs, batches
     line = {"metric": "MARL_PARTIAL ms per env step of E envs: fused rollout vs the step loop",

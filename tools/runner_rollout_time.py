@@ -9,6 +9,12 @@ Legs, each a whole run (reset, the episode, the end-of-run totals) built from on
   collect_eps0  (c) collect(eps=0): pure shortest-path descent (episodes end early)
   collect_eps1  (d) collect(eps=1): uniform random moves
   collect_noobs (e) (b) with rows->obs = NULL: no observation rows built or written
+  collect_pibt0 (f) collect(eps=0, policy="pibt"): priority inheritance with backtracking
+  collect_pibt005 (f) collect(eps=0.05, policy="pibt")
+  collect_pibt1 (f) collect(eps=1, policy="pibt")
+The policy legs also report what their last run came to: the share of envs that ended with
+every agent on its goal and the collisions per episode (the device's total_coll, read from
+the state row after each env's last step).
   reset_only    reset() alone -- the new zeroed EpisodeBatch, the env reset, row 0 -- which
                 every leg above pays once per run; `net` figures are a leg minus this one
 
@@ -38,7 +44,9 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 HBM_BYTES_PER_S = 8e12
-LEGS = ("run_table", "collect_table", "collect_eps0", "collect_eps1", "collect_noobs", "reset_only")
+LEGS = ("run_table", "collect_table", "collect_eps0", "collect_eps1", "collect_noobs", "collect_pibt0",
+        "collect_pibt005", "collect_pibt1", "reset_only")
+POLICY_LEGS = ("collect_eps0", "collect_eps1", "collect_pibt0", "collect_pibt005", "collect_pibt1")
 
 
 class TableMAC:
@@ -107,7 +115,9 @@ def main():
 
     fns = {"run_table": lambda r: r.run(), "collect_table": lambda r: r.collect(actions=table),
            "collect_eps0": lambda r: r.collect(eps=0.0), "collect_eps1": lambda r: r.collect(eps=1.0),
-           "collect_noobs": noobs, "reset_only": lambda r: r.reset()}
+           "collect_noobs": noobs, "collect_pibt0": lambda r: r.collect(eps=0.0, policy="pibt"),
+           "collect_pibt005": lambda r: r.collect(eps=0.05, policy="pibt"),
+           "collect_pibt1": lambda r: r.collect(eps=1.0, policy="pibt"), "reset_only": lambda r: r.reset()}
     runners, ep_steps, kernels = {}, {}, {}
     for leg in LEGS:                      # warm every leg: first batch, caches, code objects
         r = runners[leg] = make()
@@ -157,6 +167,8 @@ def main():
     by = {"run_table": bench.partial_bytes_per_env_step(N, D, S * S, gd) - 4 * D * N + rows_b(True) + 3 * 8 * N,
           "collect_table": collect_b(True, False, T), "collect_eps0": collect_b(True, True, T),
           "collect_eps1": collect_b(True, True, T), "collect_noobs": collect_b(False, False, T),
+          "collect_pibt0": collect_b(True, True, T), "collect_pibt005": collect_b(True, True, T),
+          "collect_pibt1": collect_b(True, True, T),
           "reset_only": 0}
     res = {}
     for leg in LEGS:
@@ -166,6 +178,12 @@ def main():
                     "episode_steps": ep_steps[leg], "runs_per_window": runs[leg], "kernel": kernels[leg],
                     "bytes_per_step": round(B * by[leg], 1),
                     "roofline_share_at_min": round(B * by[leg] / (min(per) * 1e-6) / HBM_BYTES_PER_S, 5)}
+    for leg in POLICY_LEGS:               # the leg's last run, from its batch and env state
+        r = runners[leg]
+        last = r._ep_length.to(r.batch["state"].device).long().clamp(max=limit)
+        coll = r.batch["state"][torch.arange(B, device=last.device), last, 0]
+        res[leg]["completed_share"] = round(float(r.env.at_goal.bool().all(1).float().mean().item()), 4)
+        res[leg]["collisions_per_episode"] = round(float(coll.float().mean().item()), 3)
     reset_us = float(np.median(us["reset_only"]))
     for leg in LEGS[:-1]:
         net = [(v - reset_us) / ep_steps[leg] for v in us[leg]]
