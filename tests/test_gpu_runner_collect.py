@@ -32,11 +32,12 @@ EINVAL = -1
 
 
 def _runner(tmp_path, name, grid, runs, padded=False, seed=0, tag="m"):
-    """A runner over `grid` playing runs[ep % RUNS]'s instances, with no MAC."""
+    """A runner over `grid` playing runs[ep % RUNS]'s instances, with no MAC.  name: a matrix
+    case, or a dict of its form (N, win, K, B, limit)."""
     import torch
     from mapfx.episode import OneHot
     from mapfx.runners import ParallelRunner
-    case = CASES[name]
+    case = name if isinstance(name, dict) else CASES[name]
     mp = tmp_path / (tag + ".map")
     mp.write_text("type octile\nheight %d\nwidth %d\nmap\n%s\n" % (len(grid), len(grid[0]), "\n".join(grid)))
     N, B = case["N"], case["B"]
