@@ -88,6 +88,58 @@ int mapfx_partial_rollout_runner(mapfx_partial_t* h, const mapfx_partial_state* 
                                  int action_dtype, const mapfx_partial_policy* pol, const mapfx_runner_acts* ra,
                                  const mapfx_runner_roll* rr, void* stream);
 int mapfx_partial_runner_rollout_offered(const mapfx_partial_t* h, int policy);
+
+#ifdef MAPFX_SPLIT_PROBE
+// ---- split protocol probe: libmapfx_probe.so only (mapfx.hip compiled with
+// -DMAPFX_SPLIT_PROBE); no product path loads that library.  tests/split_protocol.py
+// mirrors these numbers. ----
+// the LDS resources the split rollout's three waves share
+enum { MAPFX_PR_MAP, MAPFX_PR_INFO, MAPFX_PR_EDGE, MAPFX_PR_IMG, MAPFX_PR_CODE, MAPFX_PR_RTAB, MAPFX_PR_STAGE };
+// access kinds; SHARE: a write to the wave's own part of a slot the waves fill together
+enum { MAPFX_PK_R, MAPFX_PK_W, MAPFX_PK_RMW, MAPFX_PK_SHARE };
+// annotated sites: the step wave's (role 0) and the store waves' (roles 1 and 2, parity role - 1)
+enum {
+  MAPFX_PS_MAP_BUILD,    // every role: its rows of both padded maps (prologue)
+  MAPFX_PS_STAGE_COMMIT, // every role: its staged action rows and flag byte (prologue)
+  MAPFX_PS_MAP_INIT,     // step: the agents counted into both maps
+  MAPFX_PS_STAGE_FIRST,  // step: the three flags and row 0
+  MAPFX_PS_MAP_RESET,    // step: autoreset re-count in map s & 1
+  MAPFX_PS_MAP_MOVE,     // step: step s's move in map s & 1
+  MAPFX_PS_STAGE_NEXT,   // step: the next step's action row
+  MAPFX_PS_EDGE_PREV,    // step: edge counts of step s - 1
+  MAPFX_PS_INFO_W,       // step: info words of step s
+  MAPFX_PS_EDGE_LAST,    // step: edge counts of the launch's last step (slot 2)
+  MAPFX_PS_RTAB_W,       // store: its half of the reward table
+  MAPFX_PS_INFO_R,       // store a(q)
+  MAPFX_PS_MAP_R,        // store a(q): window rows of map q & 1
+  MAPFX_PS_IMG_W,        // store a(q): the staged records
+  MAPFX_PS_IMG_R,        // store b(q)
+  MAPFX_PS_EDGE_R,       // store b(q)
+  MAPFX_PS_CODE_W,       // store b(q): reward codes, ring row q & 31
+  MAPFX_PS_FOLD,         // store: a batch's ring rows and the reward table
+  MAPFX_PS_COUNT
+};
+#define MAPFX_SPLIT_PROBE_CAP 1024        // records per wave: enough for T <= 130
+#define MAPFX_SPLIT_PROBE_STAGE_FLAGS 64  // STAGE slot of the flag bytes (rows are slots 0 .. 63)
+typedef struct mapfx_split_probe_cfg {
+  int32_t block;            // the traced workgroup (blockIdx.x), -1: none
+  int32_t delay_role;       // the wave that sleeps before its accesses at delay_site, -1: none
+  int32_t delay_site;
+  int32_t delay_len;        // sleeps of about 2000 cycles each, at most 64
+  int32_t early_last_fold;  // != 0: the launch's last fold in interval T (negative control)
+} mapfx_split_probe_cfg;
+// rec[role][i]: word 0 = i | barriers passed << 16, word 1 = site | resource << 8 |
+// kind << 12 | slot << 16 | (tag + 1) << 24 (tag: the step the data belongs to, -1 none)
+typedef struct mapfx_split_probe_trace {
+  uint32_t n[3];
+  uint32_t barriers[3];
+  uint32_t overflow;  // a wave had more than MAPFX_SPLIT_PROBE_CAP records
+  uint32_t pad;
+  uint32_t rec[3][MAPFX_SPLIT_PROBE_CAP][2];
+} mapfx_split_probe_trace;
+int mapfx_split_probe_config(const mapfx_split_probe_cfg* cfg);
+int mapfx_split_probe_read(mapfx_split_probe_trace* out);
+#endif
 #ifdef __cplusplus
 }
 

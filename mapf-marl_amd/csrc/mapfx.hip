@@ -1461,7 +1461,67 @@ constexpr uint32_t SF_DONE = 1, SF_LIVE = 2, SF_DNOLD = 4, SF_ENVC = 8, SF_SKIP 
 
 // Workgroup barrier that waits for this wave's LDS traffic only: outstanding
 // global stores stay in flight (a __syncthreads() would drain them every step).
+#ifndef MAPFX_SPLIT_PROBE
 __device__ __forceinline__ void split_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+#define SPLIT_ACC(site, res, slot, tag, kind) \
+  do {                                        \
+  } while (0)
+#define SPLIT_DELAY(site) \
+  do {                    \
+  } while (0)
+#else
+// Probe build only (libmapfx_probe.so, never the shipped library; internal.h, "split
+// protocol probe"): every access of the three waves to LDS they share is annotated with
+// SPLIT_ACC right next to it.  In the traced workgroup lane 0 of each wave appends
+// (program-order index, barriers passed, site, resource, slot, tag, kind) to its wave's own
+// log -- plain stores, no counter shared between waves -- and tests/split_protocol.py
+// checks the three logs against the documented schedule.  A wave whose
+// role and site match the config first sleeps a fixed number of times: bounded, no memory
+// polled, no barrier added or moved.
+__device__ mapfx_split_probe_cfg g_probe_cfg = {-1, -1, -1, 0, 0};
+__device__ mapfx_split_probe_trace g_probe_trace;
+
+__device__ __forceinline__ int split_probe_role() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
+__device__ __forceinline__ bool split_probe_traced() {
+  return (int)blockIdx.x == g_probe_cfg.block && (threadIdx.x & 63) == 0;
+}
+__device__ __forceinline__ void split_probe_delay(int site) {
+  const int role = split_probe_role();
+  // wave-uniform trip count: only the configured wave ever reaches the s_sleep
+  const int n = __builtin_amdgcn_readfirstlane(
+      g_probe_cfg.delay_role == role && g_probe_cfg.delay_site == site ? min(g_probe_cfg.delay_len, 64) : 0);
+  __builtin_amdgcn_sched_barrier(0);
+  for (int i = 0; i < n; ++i) __builtin_amdgcn_s_sleep(31);  // ~2000 cycles each
+  __builtin_amdgcn_sched_barrier(0);
+}
+// (out of line: inlined at every site of every instance it made this unit the longest to compile)
+__device__ __attribute__((noinline)) void split_probe_log(int site, int res, int slot, int tag, int kind) {
+  if (split_probe_traced()) {
+    const int role = split_probe_role();
+    const uint32_t n = g_probe_trace.n[role];
+    if (n < MAPFX_SPLIT_PROBE_CAP) {
+      g_probe_trace.rec[role][n][0] = n | (g_probe_trace.barriers[role] << 16);
+      g_probe_trace.rec[role][n][1] = (uint32_t)site | ((uint32_t)res << 8) | ((uint32_t)kind << 12) |
+                                      ((uint32_t)(slot & 0xFF) << 16) | ((uint32_t)((tag + 1) & 0xFF) << 24);
+      g_probe_trace.n[role] = n + 1;
+    } else {
+      g_probe_trace.overflow = 1;
+    }
+  }
+}
+#define SPLIT_DELAY(site) split_probe_delay(site)
+#define SPLIT_ACC(site, res, slot, tag, kind) \
+  do {                                        \
+    split_probe_delay(site);                  \
+    split_probe_log(site, res, slot, tag, kind); \
+  } while (0)
+// the barrier itself is the shipped one; behind it the wave counts it (the prologue
+// barrier is number 0: interval k lies between barriers k and k + 1)
+__device__ __forceinline__ void split_barrier() {
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  if (split_probe_traced()) g_probe_trace.barriers[split_probe_role()] += 1;
+}
+#endif
 
 // ---- action staging: a launch's int8 actions in LDS, fetched once in the prologue ----
 // With every lane group full the workgroup's envs (64 / LL envs of LL agents) own 64
@@ -1516,6 +1576,23 @@ __device__ __forceinline__ void stage_commit(const stage_v4 (&v)[SPLIT_STAGE_PAS
   const bool any = __ballot(bad != 0) != 0;
   if (lane == 0) stage[wave] = any ? 1 : 0;
 }
+#ifdef MAPFX_SPLIT_PROBE
+// stage_commit's LDS writes: the wave's own flag byte and the whole rows
+// SPLIT_STAGE_ROWS p + 16 wave + (0 .. 15) below T
+__device__ __forceinline__ void split_probe_stage_commit(int T, int wave) {
+  split_probe_delay(MAPFX_PS_STAGE_COMMIT);
+  split_probe_log(MAPFX_PS_STAGE_COMMIT, MAPFX_PR_STAGE, MAPFX_SPLIT_PROBE_STAGE_FLAGS, -1, MAPFX_PK_SHARE);
+  for (int p = 0; p < SPLIT_STAGE_PASSES; ++p)
+    for (int i = 0; i < 16; ++i)
+      if (p * SPLIT_STAGE_ROWS + 16 * wave + i < T)
+        split_probe_log(MAPFX_PS_STAGE_COMMIT, MAPFX_PR_STAGE, p * SPLIT_STAGE_ROWS + 16 * wave + i, -1, MAPFX_PK_W);
+}
+#define SPLIT_ACC_STAGE_COMMIT(T, wave) split_probe_stage_commit(T, wave)
+#else
+#define SPLIT_ACC_STAGE_COMMIT(T, wave) \
+  do {                                  \
+  } while (0)
+#endif
 
 // Store policy of the store waves ("Store policy").  PLAIN leaves the line
 // dirty in the XCD's L2: right for the tiny per-env outputs, whose partial lines merge there.
@@ -1587,6 +1664,7 @@ __device__ __forceinline__ void split_store_wave_dbm(const Geo& g, const Args& a
   uint32_t k_nc = 0, k_nb = 0, k_fl = 0, k_t = 0, k_node = 0;  // step q's, kept from a to b
   const __amdgpu_buffer_rsrc_t rrec = split_rsrc(OCC ? a.obs_window_occ : a.obs_window);
 
+  SPLIT_ACC(MAPFX_PS_RTAB_W, MAPFX_PR_RTAB, par, -1, MAPFX_PK_W);
   for (int c = lane + 64 * par; c < NCODE; c += 128) {  // the code reward table (as the ALT waves)
     double rr = 0.0;  // exact fp64 op order of the reference
     if (c & SF_LIVE) {
@@ -1600,6 +1678,12 @@ __device__ __forceinline__ void split_store_wave_dbm(const Geo& g, const Args& a
     rtab[c] = rr;
   }
   auto fold_batch = [&](uint32_t q0, int cnt) {  // one (env, step) per lane, agent order
+#ifdef MAPFX_SPLIT_PROBE
+    SPLIT_DELAY(MAPFX_PS_FOLD);
+    for (int r = 0; r < cnt; ++r)
+      split_probe_log(MAPFX_PS_FOLD, MAPFX_PR_CODE, (int)((q0 + r) & 31), (int)(q0 + r), MAPFX_PK_R);
+    for (int r = 0; r < 2; ++r) split_probe_log(MAPFX_PS_FOLD, MAPFX_PR_RTAB, r, -1, MAPFX_PK_R);
+#endif
     const int j = lane & 15, e = lane >> 4;
     if (j < cnt && e < 64 / LL) {
       double R = 0.0;
@@ -1631,11 +1715,13 @@ __device__ __forceinline__ void split_store_wave_dbm(const Geo& g, const Args& a
     }
   };
   auto part_a = [&](uint32_t q) {
+    SPLIT_ACC(MAPFX_PS_INFO_R, MAPFX_PR_INFO, (int)(q & 1), (int)q, MAPFX_PK_R);
     const u32x4 iv = inf[(q & 1) * 64 + lane];
     const uint32_t* m32 = (const uint32_t*)((q & 1) ? m1 : m0) + (slot * g.map_env_bytes >> 2);
     const int nc = (int)iv.x;
     const int w0 = (nc - H2 * pitch - H2) >> 2;
     uint32_t qx[3 * WIN];
+    SPLIT_ACC(MAPFX_PS_MAP_R, MAPFX_PR_MAP, (int)(q & 1), (int)q, MAPFX_PK_R);
 #pragma unroll
     for (int y = 0; y < WIN; ++y) {
       qx[y] = m32[w0 + y * wpr];
@@ -1643,6 +1729,7 @@ __device__ __forceinline__ void split_store_wave_dbm(const Geo& g, const Args& a
       qx[2 * WIN + y] = WIN > 5 ? m32[w0 + y * wpr + 2] : 0u;
     }
     const int o = (nc - H2) & 3;
+    SPLIT_ACC(MAPFX_PS_IMG_W, MAPFX_PR_IMG, par, (int)q, MAPFX_PK_W);
     if constexpr (OCC) {
       uint32_t R[(WIN * WIN + 3) / 4 + 1];
       occ_words<WIN>(qx, o, R);
@@ -1659,11 +1746,14 @@ __device__ __forceinline__ void split_store_wave_dbm(const Geo& g, const Args& a
   };
   auto part_b = [&](uint32_t q) {
     u32x4 rv[NRC];
+    SPLIT_ACC(MAPFX_PS_IMG_R, MAPFX_PR_IMG, par, (int)q, MAPFX_PK_R);
 #pragma unroll
     for (int k = 0; k < NRC; ++k) rv[k] = ost[(k < NRC - 1 || lane + 64 * k < RCH) ? lane + 64 * k : 0];
     // (the last step's count has its own slot: the step wave writes it while b(T - 3) may
     // still read slot (T - 1) & 1)
+    SPLIT_ACC(MAPFX_PS_EDGE_R, MAPFX_PR_EDGE, (int)(q + 1 == (uint32_t)T ? 2u : (q & 1)), (int)q, MAPFX_PK_R);
     const uint32_t edge = ering[(q + 1 == (uint32_t)T ? 2u : (q & 1)) * 64 + lane];
+    SPLIT_ACC(MAPFX_PS_CODE_W, MAPFX_PR_CODE, (int)(q & 31), (int)q, MAPFX_PK_W);
     cring[(q & 31) * 64 + lane] =
         (code_t)(k_node | (k_fl & (SF_LIVE | SF_DNOLD | SF_ENVC)) | ((edge & (WIDE ? 0x3Fu : 0xFu)) << 4));
     const uint32_t roff = (q * EN + ag0) * (uint32_t)REC;
@@ -1701,6 +1791,11 @@ __device__ __forceinline__ void split_store_wave_dbm(const Geo& g, const Args& a
   // (barrier T), so its wave runs a(T - 1) and b(T - 1) back to back in the last interval
   // instead of spending one more barrier interval on b(T - 1) alone
   const int rounds = T > 0 ? T : 0;
+#ifdef MAPFX_SPLIT_PROBE
+  // negative control of the trace test: the launch's last fold where it ran before the
+  // barrier-T + 1 fix, in interval T.  Same addresses, same barrier count.
+  const bool probe_early = __builtin_amdgcn_readfirstlane(g_probe_cfg.early_last_fold) != 0;
+#endif
   for (int s = 1; s <= rounds; ++s) {
 #ifdef MAPFX_STAMPS  // diagnostic: end of round s - 1's work (columns 5 / 7 of row s - 1)
     if (s > 1) {
@@ -1716,6 +1811,12 @@ __device__ __forceinline__ void split_store_wave_dbm(const Geo& g, const Args& a
       if (q == T - 1) {  // the last step: its b part right away (own staged record: LDS order)
         wave_fence();
         part_b((uint32_t)q);
+#ifdef MAPFX_SPLIT_PROBE
+        if (probe_early) {
+          wave_fence();
+          fold_batch((uint32_t)(T - 1) & ~15u, ((T - 1) & 15) + 1);
+        }
+#endif
       }
     } else if (q >= 1) {
       part_b((uint32_t)(q - 1));
@@ -1724,6 +1825,9 @@ __device__ __forceinline__ void split_store_wave_dbm(const Geo& g, const Args& a
   // barrier T + 1 (the step wave meets it after its state write-back): codes T - 2 (the
   // other wave's) and T - 1 (this wave's) are both in the ring
   split_barrier();
+#ifdef MAPFX_SPLIT_PROBE
+  if (probe_early) return;
+#endif
   if (T > 0 && ((T - 1) & 1) == par) fold_batch((uint32_t)(T - 1) & ~15u, ((T - 1) & 15) + 1);
 }
 
@@ -1793,15 +1897,19 @@ __global__ void __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : 64, SPLIT ? SPLIT_W
         asm volatile("" ::"s"(g0.map_words), "s"(a0.do_step), "s"(g0.wv_off_dep), "s"(g0.wv_off_bits),
                      "s"(g0.wv_off_rew));
         stage_fetch();
+        SPLIT_ACC(MAPFX_PS_MAP_BUILD, MAPFX_PR_MAP, 0, -1, MAPFX_PK_SHARE);
+        SPLIT_ACC(MAPFX_PS_MAP_BUILD, MAPFX_PR_MAP, 1, -1, MAPFX_PK_SHARE);
         build_map_rows_fast<MAPFX_FAST_WPR, 1>(g, (uint32_t*)(lds + g.wv_off_map + sl * g.map_env_bytes), src,
                                                bl, LL * SPLIT_WAVES, pf,
                                                (uint32_t*)(lds + g.wv_off_split + sl * g.map_env_bytes));
       } else {
         stage_fetch();
       }
-      if (a.act_stage)
+      if (a.act_stage) {
+        SPLIT_ACC_STAGE_COMMIT(a.T, swave);
         stage_commit(sv, lds + g.wv_off_split + (64 / LL) * g.map_env_bytes + split_tail_lds(RECB, LL), a.T,
                      (int)(threadIdx.x >> 2), swave, (int)(threadIdx.x & 63));
+      }
       split_barrier();  // + the staged actions and the waves' flags
       const int par = (int)(threadIdx.x >> 6) - 1;            // this wave's step parity
       // [M1: 64 / LL maps][info: 2 steps][edge: 2 steps][staged records: 2 waves][fold]
@@ -1963,6 +2071,10 @@ __global__ void __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : 64, SPLIT ? SPLIT_W
   // the split's second count map M1 (odd steps) of this env, at the start of the split region
   constexpr bool DBM = SPLIT;
   uint32_t* m1_32 = DBM ? (uint32_t*)(lds + g.wv_off_split + slot * g.map_env_bytes) : nullptr;
+  if constexpr (SPLIT) {  // (the fallback builder below: the step wave's rows are all rows)
+    SPLIT_ACC(MAPFX_PS_MAP_BUILD, MAPFX_PR_MAP, 0, -1, MAPFX_PK_SHARE);
+    SPLIT_ACC(MAPFX_PS_MAP_BUILD, MAPFX_PR_MAP, 1, -1, MAPFX_PK_SHARE);
+  }
   if (g.wv_fast) build_map_rows_fast<MAPFX_FAST_WPR, RPF>(g, map32, bsrc, bl, bnl, pfw, m1_32);
   else build_map_rows_c(g, map32, bitsL, ag, L);
   if (DBM && !g.wv_fast) {  // (the fallback builder fills M0 alone: copy it)
@@ -1975,6 +2087,7 @@ __global__ void __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : 64, SPLIT ? SPLIT_W
   if constexpr (SPLIT) {
     if (stage) {
       if (t_long) sv[0] = sv0e;
+      SPLIT_ACC_STAGE_COMMIT(T, 0);
       stage_commit(sv, stg, T, lane64 >> 2, 0, lane64);
     }
     split_barrier();  // + the store waves' map rows, action rows and flags
@@ -1982,6 +2095,10 @@ __global__ void __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : 64, SPLIT ? SPLIT_W
     wave_fence();
   }
   PSTAMP(2);
+  if constexpr (SPLIT) {  // the agents counted into both maps, after the prologue barrier
+    SPLIT_ACC(MAPFX_PS_MAP_INIT, MAPFX_PR_MAP, 0, -1, MAPFX_PK_RMW);
+    SPLIT_ACC(MAPFX_PS_MAP_INIT, MAPFX_PR_MAP, 1, -1, MAPFX_PK_RMW);
+  }
   if (has) atomicAdd(&map32[cur >> 2], 1u << ((cur & 3) * 8));
   if (DBM && has) atomicAdd(&m1_32[cur >> 2], 1u << ((cur & 3) * 8));
   wave_fence();
@@ -2232,6 +2349,7 @@ __global__ void __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : 64, SPLIT ? SPLIT_W
           // the last step ended these envs' episodes (their agents are back at init_pos,
           // mapf_gridworld.py:70-83): count them there in this step's map -- intact since
           // barrier s - 1's readers are done -- and read their neighbours
+          SPLIT_ACC(MAPFX_PS_MAP_RESET, MAPFX_PR_MAP, ODD ? 1 : 0, s, MAPFX_PK_RMW);
           if (reset_pending) {
             const int cpi = cpr;
             atomicAdd(&mp32[cpi >> 2], cpi != cur ? 0u - (1u << ((cpi & 3) * 8)) : 0u);
@@ -2269,6 +2387,7 @@ __global__ void __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : 64, SPLIT ? SPLIT_W
       const int nc = moved ? oc + dlt : oc;
       dep[oc] = (unsigned char)(moved ? (uint32_t)act : 0x7Fu);
       const int cpi = cpr;
+      SPLIT_ACC(MAPFX_PS_MAP_MOVE, MAPFX_PR_MAP, ODD ? 1 : 0, s, MAPFX_PK_RMW);
       atomicAdd(&mp32[cpi >> 2], cpi != nc ? 0u - (1u << ((cpi & 3) * 8)) : 0u);
       atomicAdd(&mp32[nc >> 2], cpi != nc ? 1u << ((nc & 3) * 8) : 0u);
       cpr = nc;
@@ -2278,7 +2397,10 @@ __global__ void __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : 64, SPLIT ? SPLIT_W
       // occupant's move (the edge test)
       const uint32_t n_up = mp[nc - pitch], n_dw = mp[nc + pitch], n_lf = mp[nc - 1], n_rt = mp[nc + 1];
       const uint32_t dj = dep[nc];
-      if constexpr (STG) act_nx = srows[min(s + 1, T - 1) * 64];  // the next step's action
+      if constexpr (STG) {
+        SPLIT_ACC(MAPFX_PS_STAGE_NEXT, MAPFX_PR_STAGE, min(s + 1, T - 1), -1, MAPFX_PK_R);
+        act_nx = srows[min(s + 1, T - 1) * 64];  // the next step's action
+      }
       STAMP(1);
       // C: step s - 1's edge count (:364-383), for the store wave's b part (counting it in
       // the store waves' a part instead, from old / new cell, action and the occupant's move
@@ -2286,6 +2408,7 @@ __global__ void __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : 64, SPLIT ? SPLIT_W
       // 25.2 vs 21.6 us at C2 T = 20, gpurun_out/r04o: kept here)
       if (s > 0) {
         const int e = edge_of();
+        SPLIT_ACC(MAPFX_PS_EDGE_PREV, MAPFX_PR_EDGE, ODD ? 0 : 1, s - 1, MAPFX_PK_W);
         ering[(ODD ? 0 : 1) * 64 + lane64] = (unsigned char)(e > 255 ? 255 : e);
       }
       STAMP(3);
@@ -2300,6 +2423,7 @@ __global__ void __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : 64, SPLIT ? SPLIT_W
       const bool alldone = (__ballot(!dn) & envmask) == 0;
       const uint32_t fl = (dn ? SF_DONE : 0u) | (live ? SF_LIVE : 0u) | (dn_old ? SF_DNOLD : 0u) |
                           (envc ? SF_ENVC : 0u) | (skip ? SF_SKIP : 0u) | (alldone ? SF_ALLDONE : 0u);
+      SPLIT_ACC(MAPFX_PS_INFO_W, MAPFX_PR_INFO, ODD ? 1 : 0, s, MAPFX_PK_W);
       info[(ODD ? 1 : 0) * 64 + lane64] = u32x4{(uint32_t)nc, nbn, fl, (uint32_t)tcur};
       q_oc = oc;
       q_nc = nc;
@@ -2310,6 +2434,7 @@ __global__ void __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : 64, SPLIT ? SPLIT_W
       nb = nbn;
       if (s == T - 1) {  // the last step's edge count now (slot 2): its b part runs next interval
         const int e = edge_of();
+        SPLIT_ACC(MAPFX_PS_EDGE_LAST, MAPFX_PR_EDGE, 2, s, MAPFX_PK_W);
         ering[2 * 64 + lane64] = (unsigned char)(e > 255 ? 255 : e);
       }
       if constexpr (AR) {
@@ -2348,6 +2473,8 @@ __global__ void __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : 64, SPLIT ? SPLIT_W
     };
     if (stage) {
       // (byte 3 of the flag word is no wave's)
+      SPLIT_ACC(MAPFX_PS_STAGE_FIRST, MAPFX_PR_STAGE, MAPFX_SPLIT_PROBE_STAGE_FLAGS, -1, MAPFX_PK_R);
+      SPLIT_ACC(MAPFX_PS_STAGE_FIRST, MAPFX_PR_STAGE, 0, -1, MAPFX_PK_R);
       const bool bad = __builtin_amdgcn_readfirstlane(*(const uint32_t*)stg & 0xFFFFFFu) != 0;
       act_nx = srows[0];
       if (a.autoreset) {
@@ -3012,6 +3139,26 @@ const char* mapfx_last_kernel(void) {
 
 // error hook for the other translation unit of the library (partial.hip)
 int mapfx_internal_error(int code, const char* msg) { return set_error(code, "%s", msg); }
+
+#ifdef MAPFX_SPLIT_PROBE
+// the config for the launches that follow, and the three waves' logs cleared
+int mapfx_split_probe_config(const mapfx_split_probe_cfg* cfg) {
+  static const uint32_t zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // n, barriers, overflow, pad
+  static_assert(offsetof(mapfx_split_probe_trace, rec) == sizeof(zero), "trace header");
+  if (!cfg) return set_error(MAPFX_EINVAL, "NULL cfg");
+  int rc = check_hip(hipDeviceSynchronize(), "probe config: synchronize");
+  if (!rc) rc = check_hip(hipMemcpyToSymbol(HIP_SYMBOL(g_probe_cfg), cfg, sizeof(*cfg)), "probe config");
+  if (!rc) rc = check_hip(hipMemcpyToSymbol(HIP_SYMBOL(g_probe_trace), zero, sizeof(zero)), "probe trace clear");
+  return rc;
+}
+// the logs of the launches since the last mapfx_split_probe_config (the device is drained first)
+int mapfx_split_probe_read(mapfx_split_probe_trace* out) {
+  if (!out) return set_error(MAPFX_EINVAL, "NULL out");
+  int rc = check_hip(hipDeviceSynchronize(), "probe read: synchronize");
+  if (!rc) rc = check_hip(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_probe_trace), sizeof(*out)), "probe read");
+  return rc;
+}
+#endif
 
 #ifdef MAPFX_STAMPS
 int mapfx_debug_stamps(unsigned long long* host_out) {
