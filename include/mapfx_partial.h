@@ -17,8 +17,9 @@
  * Same conventions as mapfx.h: caller-owned DEVICE pointers, (row, col) int32
  * positions, LSB-first obstacle bitmaps of mapfx_map_stride(H, W) bytes per env,
  * asynchronous on `stream`, 0 / negative MAPFX_E* return codes, messages from
- * mapfx_last_error().  Not restated (out of scope): the `output`
- * mode's random collision repair (:262-275) and the visualisation hooks.
+ * mapfx_last_error().  Not part of this ABI: the visualisation hooks, and the `output`
+ * mode's random collision repair (:262-275), which the drop-in env
+ * (mapfx/envs/marl_partial.py) runs on the host around these calls.
  *
  * Limits: N <= 1024, H <= 1024, W <= 1536, and for a side above 256 the BFS
  * frontier rows must fit LDS: H * ceil(W / 64) * 8 bytes plus the BFS kernel's few

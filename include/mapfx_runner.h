@@ -155,6 +155,61 @@ int mapfx_runner_rollout(mapfx_partial_t* h, const mapfx_partial_state* st,
 /* 1 where the call is offered (policy != 0: in policy mode), else 0 */
 int mapfx_runner_rollout_offered(const mapfx_partial_t* h, int policy);
 
+/* Action selection on the device: PyMARL's EpsilonGreedyActionSelector and
+ * MultinomialActionSelector (components/action_selectors.py:54-71, :23-37) as one launch,
+ * its random words counter-based and keyed by the GLOBAL env id like every other stream of
+ * the library -- so the actions of an env do not depend on which other rows the call holds
+ * (the runner's padded or exact `bs`, a sharded or an unsharded run).  Additive exports (the
+ * ABI version is unchanged).  The rule is defined by mapfx.rng.select_actions; restated:
+ *
+ * Row j belongs to global env gid = env_offset + (env_ids ? env_ids[j] : j); agent a of it
+ * draws the word
+ *   u = splitmix64(seed ^ gid*K_ENV ^ (uint32)t*K_T ^ a*K_AGENT ^ 0x700*K_STREAM)
+ * (mapfx_select_word; the K_* of mapfx/rng.py, 0x700 = STREAM_SELECT).  m_i = action i is
+ * available (avail NULL: every action).  greedy(v) = the first index of the maximum, a NaN
+ * greater than every number (the first NaN wins), 0 when every entry is -inf: what
+ * torch.max(dim)[1] returns on the CPU.
+ *   MAPFX_SELECT_EPS_GREEDY: v_i = m_i ? q_i : -inf, g = greedy(v).  explore = !greedy_only
+ *     && (u >> 32) < eps_q (eps_q = round(eps * 2^32): 0 never, 2^32 always, as in
+ *     mapfx_partial_policy).  n = popcount(m).  explore && n > 0: the k-th available index
+ *     in ascending order, k = ((u & 0xFFFFFFFF) * n) >> 32; else g (0 when nothing is
+ *     available, where torch's Categorical raises).
+ *   MAPFX_SELECT_MULTINOMIAL: p_i = m_i ? q_i : 0.0f.  greedy_only: greedy(p) (the masked
+ *     zeros take part, as in the reference).  Else the float32 prefix sums c_0 = p_0, c_i =
+ *     c_{i-1} + p_i in this order and s = c_{A-1}; s not a finite number above 0: greedy(p);
+ *     else r = float((u & 0xFFFFFFFF) >> 8) * 2^-24 (exact), x = r * s (one float32
+ *     rounding), and the action is the first i with c_i > x, or, if there is none, the last
+ *     i with p_i > 0.
+ * The distribution is the reference's (a uniform available action with probability eps,
+ * else the greedy one; a draw from p / s); the numbers are this library's, not torch's.
+ *
+ * One launch of select_kernel<5> (A == 5) or select_kernel<0> (any other A), reported by
+ * mapfx_last_kernel(); asynchronous on `stream`, no allocation, no host synchronisation,
+ * graph-capturable.  rows == 0: MAPFX_OK, no launch.  MAPFX_EINVAL before any launch: NULL
+ * a, q or actions; rows < 0, N < 1, A outside 1..9, rows * N >= 2^31; an unknown mode or
+ * avail_form; eps_q > 2^32; a row stride smaller than the row.  An env_ids entry is used as
+ * given: a padded duplicate computes the same actions as the row it duplicates. */
+#define MAPFX_SELECT_EPS_GREEDY 0
+#define MAPFX_SELECT_MULTINOMIAL 1
+#define MAPFX_AVAIL_I32 0
+#define MAPFX_AVAIL_BITS 1
+typedef struct mapfx_select_args {
+  int32_t rows, N, A;            /* A in 1..9 */
+  const float* q;     int64_t q_sr;       /* [rows][N][A], row stride in elements */
+  const void* avail;  int64_t avail_sr;   /* NULL: every action available */
+  int32_t avail_form; /* MAPFX_AVAIL_I32: int32 [rows][N][A], != 0 = available (EpisodeBatch rows);
+                         MAPFX_AVAIL_BITS: [rows][N] bit i = action i, u8 for A <= 8, u16 for A == 9
+                         (the avail / next_mask outputs of the env calls) */
+  const int64_t* env_ids;        /* [rows] or NULL: the runner's bs */
+  int64_t env_offset;
+  uint64_t seed, eps_q;          /* eps_q in 0 .. 2^32 */
+  int32_t t, mode, greedy_only;
+  int64_t* actions;   int64_t actions_sr; /* [rows][N] out, int64: PyMARL's dtype */
+} mapfx_select_args;
+int mapfx_select_actions(const mapfx_select_args* a, void* stream);
+/* the word u above, on the host (as mapfx_action is for the action generator) */
+uint64_t mapfx_select_word(uint64_t seed, int64_t gid, int32_t t, int32_t agent);
+
 /* n int32 of host memory the device writes directly (hipHostMalloc mapped +
  * coherent): *host_ptr for the host, *dev_ptr for kernels (mapfx_runner_post's
  * counts_out).  Free with mapfx_host_ring_free(host_ptr). */

@@ -194,6 +194,161 @@ __global__ void __launch_bounds__(CT) runner_compact_kernel(mapfx_runner_state r
   }
 }
 
+// ---- action selection (mapfx_select_actions; the rule: mapfx_runner.h, mapfx/rng.py
+// select_actions) ----
+// mapfx/rng.py: K_ENV, K_T, K_AGENT, K_STREAM and the selection's stream id
+constexpr uint64_t RK_ENV = 0xD1B54A32D192ED03ull, RK_T = 0xABC98388FB8FAC03ull,
+                   RK_AGENT = 0x8CB92BA72F3D8DD7ull, RK_STREAM = 0xF1357AEA2E62A9C5ull;
+constexpr uint64_t STREAM_SELECT = 0x700;
+
+__host__ __device__ inline uint64_t select_word(uint64_t seed, int64_t gid, int32_t t, int32_t agent) {
+  return splitmix64(seed ^ ((uint64_t)gid * RK_ENV) ^ ((uint64_t)(uint32_t)t * RK_T) ^
+                    ((uint64_t)(uint32_t)agent * RK_AGENT) ^ (STREAM_SELECT * RK_STREAM));
+}
+
+// x replaces the running maximum b: torch's order, a NaN above every number and kept once met
+__device__ inline bool beats(float x, float b) { return !(b != b) && ((x != x) || x > b); }
+
+constexpr int SB = 256;  // threads of a selection workgroup: four independent waves
+
+// The wave's 64 * A dwords of a dense [rows][N][A] array (row stride N * A: one contiguous
+// run starting at the wave's first lane) into its LDS slice with A coalesced loads per lane;
+// lane l then reads dwords l * A .. l * A + A - 1 (a lane stride of A dwords: at A = 5 coprime
+// to the banks, no conflict).  The lanes past the array's end load nothing.
+template <int AM, typename T>
+__device__ inline void stage_dense(T* __restrict__ lds, const T* __restrict__ src, int A, int64_t base,
+                                   int64_t end, int lane) {
+#pragma unroll
+  for (int i = 0; i < AM; ++i) {
+    const int idx = i * 64 + lane;
+    if (i < A && base + idx < end) lds[idx] = src[base + idx];
+  }
+}
+
+// One lane per (row, agent).  AC: the compile-time number of actions, 0 = a.A at run time.
+template <int AC>
+__global__ void __launch_bounds__(SB) select_kernel(mapfx_select_args a, int dense_q, int dense_av) {
+  constexpr int AM = AC ? AC : 9;
+  const int A = AC ? AC : a.A;
+  __shared__ float s_q[SB / 64][64 * AM];
+  __shared__ int32_t s_av[SB / 64][64 * AM];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const uint32_t total = (uint32_t)a.rows * (uint32_t)a.N;  // < 2^31 (checked by the host)
+  const uint32_t wave0 = blockIdx.x * SB + wv * 64;
+  if (wave0 >= total) return;  // (wave-uniform)
+  if (dense_q) stage_dense<AM>(s_q[wv], a.q, A, (int64_t)wave0 * A, (int64_t)total * A, lane);
+  if (dense_av)
+    stage_dense<AM>(s_av[wv], (const int32_t*)a.avail, A, (int64_t)wave0 * A, (int64_t)total * A, lane);
+  wave_fence();
+  const uint32_t gl = wave0 + lane;
+  if (gl >= total) return;  // the tail lanes are off from here on: no address of theirs is formed
+  const uint32_t row = gl / (uint32_t)a.N, ag = gl - row * (uint32_t)a.N;
+
+  float v[AM];
+  unsigned m = 0;
+  const unsigned all = (1u << A) - 1u;
+  // (two loops, not one select per element: a select of the two pointers becomes a flat load)
+  if (dense_q) {
+#pragma unroll
+    for (int i = 0; i < AM; ++i)
+      if (i < A) v[i] = s_q[wv][lane * A + i];
+  } else {
+    const float* qrow = a.q + (int64_t)row * a.q_sr + (int64_t)ag * A;
+#pragma unroll
+    for (int i = 0; i < AM; ++i)
+      if (i < A) v[i] = qrow[i];
+  }
+  if (!a.avail) {
+    m = all;
+  } else if (a.avail_form == MAPFX_AVAIL_BITS) {
+    const int64_t i = (int64_t)row * a.avail_sr + ag;
+    m = (A == 9 ? (unsigned)((const uint16_t*)a.avail)[i] : (unsigned)((const uint8_t*)a.avail)[i]) & all;
+  } else if (dense_av) {
+#pragma unroll
+    for (int i = 0; i < AM; ++i)
+      if (i < A) m |= (s_av[wv][lane * A + i] != 0 ? 1u : 0u) << i;
+  } else {
+    const int32_t* arow = (const int32_t*)a.avail + (int64_t)row * a.avail_sr + (int64_t)ag * A;
+#pragma unroll
+    for (int i = 0; i < AM; ++i)
+      if (i < A) m |= (arow[i] != 0 ? 1u : 0u) << i;
+  }
+  const int64_t gid = a.env_offset + (a.env_ids ? a.env_ids[row] : (int64_t)row);
+  const uint64_t u = select_word(a.seed, gid, a.t, (int32_t)ag);
+  const uint64_t lo = u & 0xFFFFFFFFull;
+
+  // greedy(v masked with `fill`): the first maximum, NaN above all
+  const float fill = a.mode == MAPFX_SELECT_EPS_GREEDY ? -__builtin_inff() : 0.0f;
+#pragma unroll
+  for (int i = 0; i < AM; ++i)
+    if (i < A && !((m >> i) & 1u)) v[i] = fill;
+  int g = 0;
+  float best = v[0];
+#pragma unroll
+  for (int i = 1; i < AM; ++i)
+    if (i < A && beats(v[i], best)) {
+      best = v[i];
+      g = i;
+    }
+  int act = g;
+  if (a.mode == MAPFX_SELECT_EPS_GREEDY) {
+    const int n = __popc(m);
+    if (!a.greedy_only && (u >> 32) < a.eps_q && n > 0) {
+      const int k = (int)((lo * (uint64_t)n) >> 32);  // the k-th available index, ascending
+      int cnt = 0;
+#pragma unroll
+      for (int i = 0; i < AM; ++i)
+        if (i < A && ((m >> i) & 1u)) {
+          if (cnt == k) act = i;
+          ++cnt;
+        }
+    }
+  } else if (!a.greedy_only) {
+    float c[AM];
+    float s = 0.0f;
+#pragma unroll
+    for (int i = 0; i < AM; ++i)
+      if (i < A) {
+        s = i == 0 ? v[0] : __fadd_rn(s, v[i]);  // c_i = c_{i-1} + p_i, float32, in this order
+        c[i] = s;
+      }
+    if (s > 0.0f && s < __builtin_inff()) {  // a finite number above 0 (a NaN fails s > 0)
+      // r is exact (24 bits), x one float32 rounding; neither product feeds an add
+      const float r = __fmul_rn((float)(uint32_t)(lo >> 8), 0x1p-24f);
+      const float x = __fmul_rn(r, s);
+      int first = -1, last = 0;
+#pragma unroll
+      for (int i = 0; i < AM; ++i)
+        if (i < A) {
+          if (first < 0 && c[i] > x) first = i;
+          if (v[i] > 0.0f) last = i;
+        }
+      act = first >= 0 ? first : last;
+    }
+  }
+  a.actions[(int64_t)row * a.actions_sr + ag] = (int64_t)act;
+}
+
+int check_select(const mapfx_select_args* a) {
+  if (!a) return perr(MAPFX_EINVAL, "select_actions: NULL args");
+  if (a->rows < 0 || a->N < 1) return perr(MAPFX_EINVAL, "select_actions: rows < 0 or N < 1");
+  if (a->A < 1 || a->A > 9) return perr(MAPFX_EINVAL, "select_actions: A not in 1..9");
+  if ((int64_t)a->rows * a->N >= (1ll << 31)) return perr(MAPFX_EINVAL, "select_actions: rows * N must be below 2^31");
+  if (a->mode != MAPFX_SELECT_EPS_GREEDY && a->mode != MAPFX_SELECT_MULTINOMIAL)
+    return perr(MAPFX_EINVAL, "select_actions: unknown mode");
+  if (a->avail_form != MAPFX_AVAIL_I32 && a->avail_form != MAPFX_AVAIL_BITS)
+    return perr(MAPFX_EINVAL, "select_actions: unknown avail_form");
+  if (a->eps_q > (1ull << 32)) return perr(MAPFX_EINVAL, "select_actions: eps_q above 2^32");
+  if (a->rows == 0) return MAPFX_OK;
+  if (!a->q || !a->actions) return perr(MAPFX_EINVAL, "select_actions: NULL q / actions");
+  const int64_t na = (int64_t)a->N * a->A;
+  if (a->q_sr < na) return perr(MAPFX_EINVAL, "select_actions: q row stride smaller than N * A");
+  if (a->avail && a->avail_sr < (a->avail_form == MAPFX_AVAIL_BITS ? (int64_t)a->N : na))
+    return perr(MAPFX_EINVAL, "select_actions: avail row stride smaller than the row");
+  if (a->actions_sr < a->N) return perr(MAPFX_EINVAL, "select_actions: actions row stride smaller than N");
+  return MAPFX_OK;
+}
+
 int check_rs(const mapfx_runner_state* rs) {
   if (!rs || rs->B < 0 || rs->N < 1 || rs->D < 0 || !rs->alive || !rs->alive_prev || !rs->bs ||
       !rs->counts || !rs->ep_return || !rs->ep_length || !rs->env_steps || !rs->env_actions)
@@ -390,6 +545,21 @@ int mapfx_runner_rollout(mapfx_partial_t* h, const mapfx_partial_state* st, cons
   r2.bs_inv = rs->bs_inv + (int64_t)(par_end ^ 1) * rs->B;
   return launch_kernel(runner_compact_kernel, dim3(stale_map ? 2 : 1), dim3(CT), 0, (hipStream_t)stream, nullptr,
                        nullptr, "runner_compact_kernel launch", QUIET, r2, counts_out, stale_map);
+}
+
+uint64_t mapfx_select_word(uint64_t seed, int64_t gid, int32_t t, int32_t agent) {
+  return select_word(seed, gid, t, agent);
+}
+
+int mapfx_select_actions(const mapfx_select_args* a, void* stream) {
+  const int rc = check_select(a);
+  if (rc || a->rows == 0) return rc;
+  const int64_t na = (int64_t)a->N * a->A;
+  const int dense_q = a->q_sr == na;
+  const int dense_av = a->avail && a->avail_form == MAPFX_AVAIL_I32 && a->avail_sr == na;
+  const dim3 grid((unsigned)(((int64_t)a->rows * a->N + SB - 1) / SB));
+  return launch_kernel(a->A == 5 ? select_kernel<5> : select_kernel<0>, grid, dim3(SB), 0, (hipStream_t)stream,
+                       nullptr, nullptr, "select_kernel launch", NOTED, *a, dense_q, dense_av);
 }
 
 int mapfx_host_ring_alloc(int32_t n, int32_t** host_ptr, int32_t** dev_ptr) {

@@ -126,7 +126,8 @@ EXPORTS = ("mapfx_abi_version", "mapfx_last_error", "mapfx_build_id", "mapfx_las
            "mapfx_primal_blocking", "mapfx_primal_generate", "mapfx_runner_begin", "mapfx_runner_actions", "mapfx_runner_post",
            "mapfx_runner_step", "mapfx_host_ring_alloc", "mapfx_host_ring_free",
            "mapfx_partial_bind_err", "mapfx_runner_rollout", "mapfx_runner_rollout_offered",
-           "mapfx_partial_policy_rule", "mapfx_partial_policy_rule_offered")
+           "mapfx_partial_policy_rule", "mapfx_partial_policy_rule_offered",
+           "mapfx_select_actions", "mapfx_select_word")
 
 
 class ERows(ctypes.Structure):  # include/mapfx_runner.h mapfx_episode_rows
@@ -140,6 +141,16 @@ class RState(ctypes.Structure):  # include/mapfx_runner.h mapfx_runner_state
         (k, c_vp) for k in ("alive", "alive_prev", "bs", "counts", "ep_return", "ep_length",
                             "env_steps", "env_actions", "bs_inv")]
 
+
+class SelArgs(ctypes.Structure):  # include/mapfx_runner.h mapfx_select_args
+    _fields_ = [("rows", c_i32), ("N", c_i32), ("A", c_i32), ("q", c_vp), ("q_sr", c_i64),
+                ("avail", c_vp), ("avail_sr", c_i64), ("avail_form", c_i32), ("env_ids", c_vp),
+                ("env_offset", c_i64), ("seed", c_u64), ("eps_q", c_u64), ("t", c_i32),
+                ("mode", c_i32), ("greedy_only", c_i32), ("actions", c_vp), ("actions_sr", c_i64)]
+
+
+# include/mapfx_runner.h MAPFX_SELECT_* (by their Python names: rng.SELECT_MODES) and MAPFX_AVAIL_*
+MAPFX_AVAIL_I32, MAPFX_AVAIL_BITS = 0, 1
 
 ABI_VERSION = 6  # include/mapfx.h MAPFX_ABI_VERSION
 
@@ -208,6 +219,8 @@ def _load():
         "mapfx_runner_rollout": (c_i32, [c_vp, P(PState), P(RState), c_i32, c_i32, c_vp, c_i32,
                                          P(PPolicy), c_vp, P(ERows), c_vp]),
         "mapfx_runner_rollout_offered": (c_i32, [c_vp, c_i32]),
+        "mapfx_select_actions": (c_i32, [P(SelArgs), c_vp]),
+        "mapfx_select_word": (c_u64, [c_u64, c_i64, c_i32, c_i32]),
         "mapfx_host_ring_alloc": (c_i32, [c_i32, P(c_vp), P(c_vp)]),
         "mapfx_host_ring_free": (None, [c_vp]),
     }

@@ -5,8 +5,10 @@ MARL-curve-main/src/envs/marl_partial.py (`MARL_PARTIAL_ENV`, lines 23-1000); th
 goal-distance tables, transition, rewards, collisions, observations, state and
 available actions come from the HIP kernels (mapfx.partial.MarlPartialBatch,
 E = 1).  Observations are float32, the dtype PyMARL's EpisodeBatch stores them
-in.  Not reproduced (out of scope): rendering / visual json export and the
-`output=True` random collision repair (:262-275).
+in.  `output=True` repairs each step's collisions on the host with the reference's
+randomised tries (:262-275, :645-820), then re-observes on the device
+(tests/test_partial_output_mode.py).  Not reproduced (out of scope): rendering / visual
+json export.
 """
 from __future__ import annotations
 

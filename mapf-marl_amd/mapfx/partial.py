@@ -41,6 +41,7 @@ class MarlPartialBatch(DeviceBatch):
         self.E, self.N, init_pos, goals = parse_agents(init_pos, goals, "init_pos/goals")
         self.H, self.W, bits, self.map_shared = parse_map(grids, bits, hw, self.E)
         self.episode_limit = int(p["episode_limit"])
+        self.env_offset = int(env_offset)
         cfg = _abi.PCfg(H=self.H, W=self.W, n_agents=self.N, n_envs=self.E,
                         env_offset=int(env_offset), episode_limit=self.episode_limit,
                         obs_window=int(p["obs_window"]), obs_knn_agents=int(p["obs_knn_agents"]),

@@ -23,6 +23,9 @@ K_STREAM = np.uint64(0xF1357AEA2E62A9C5)
 STREAM_GEN_WORLD, STREAM_GEN_OBST, STREAM_GEN_START, STREAM_GEN_GOAL = 0x100, 0x200, 0x300, 0x400
 # Streams of the device MARL_PARTIAL scenario draw (mapfx_partial_draw, csrc/partial.hip)
 STREAM_SCEN_FILE, STREAM_SCEN_LINE = 0x500, 0x600
+# Stream of the device action selection (mapfx_select_actions, csrc/runner.hip)
+STREAM_SELECT = 0x700
+SELECT_MODES = {"epsilon_greedy": 0, "multinomial": 1}   # include/mapfx_runner.h MAPFX_SELECT_*
 
 
 def splitmix64(x):
@@ -188,6 +191,79 @@ def runner_policy_seed(seed, run):
     be replayed from its number."""
     return int(splitmix64(np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF)
                           ^ _mul(np.uint64(int(run) & 0xFFFFFFFFFFFFFFFF), K_T)))
+
+
+def select_words(seed, env_ids, t, n_agents):
+    """The selection stream's words, uint64 [len(env_ids), n_agents]:
+    splitmix64(seed ^ gid*K_ENV ^ (uint32)t*K_T ^ a*K_AGENT ^ STREAM_SELECT*K_STREAM)
+    (mapfx_select_word of include/mapfx_runner.h); env_ids are GLOBAL env ids."""
+    env = np.asarray(env_ids, dtype=np.int64).astype(np.uint64)[:, None]
+    ag = np.arange(n_agents, dtype=np.uint64)[None, :]
+    tt = np.uint64(int(t) & 0xFFFFFFFF)
+    return splitmix64(np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF) ^ _mul(env, K_ENV) ^ _mul(tt, K_T)
+                      ^ _mul(ag, K_AGENT) ^ _mul(np.uint64(STREAM_SELECT), K_STREAM))
+
+
+def greedy_index(v):
+    """The greedy index over the last axis, what torch.max(dim)[1] returns on the CPU: the
+    first index of the maximum, a NaN greater than every number (the first NaN wins), 0 when
+    every entry is -inf."""
+    v = np.asarray(v, dtype=np.float32)
+    nan = np.isnan(v)
+    with np.errstate(invalid="ignore"):
+        first_max = (np.where(nan, -np.inf, v) == np.where(nan, -np.inf, v).max(-1, keepdims=True)).argmax(-1)
+    return np.where(nan.any(-1), nan.argmax(-1), first_max).astype(np.int64)
+
+
+def select_actions(seed, env_ids, t, q, avail=None, eps_q=0, mode="epsilon_greedy", greedy_only=False):
+    """The device action selection (mapfx_select_actions, include/mapfx_runner.h), restated.
+    This function is the rule's definition.
+
+    q [rows, N, A] float32, avail [rows, N, A] (nonzero = available; None: all), env_ids
+    [rows] GLOBAL env ids, t the step counter, u = select_words(seed, env_ids, t, N).
+
+    "epsilon_greedy" (PyMARL's EpsilonGreedyActionSelector): v_i = m_i ? q_i : -inf,
+    g = greedy_index(v).  explore = not greedy_only and (u >> 32) < eps_q (eps_q = round(eps *
+    2**32), 2**32 = always).  With n = the number of available actions: explore and n > 0 takes
+    the k-th available index in ascending order, k = ((u & 0xFFFFFFFF) * n) >> 32; else g (0
+    when nothing is available).
+
+    "multinomial" (MultinomialActionSelector): p_i = m_i ? q_i : 0.  greedy_only: greedy_index(p)
+    (the masked zeros take part).  Else the float32 prefix sums c_0 = p_0, c_i = c_{i-1} + p_i
+    and s = c_{A-1}; s not a finite number above 0: greedy_index(p); else r = float((u &
+    0xFFFFFFFF) >> 8) * 2**-24 (exact), x = r * s (one float32 rounding), and the action is the
+    first i with c_i > x, or, if there is none, the last i with p_i > 0.
+
+    Returns int64 [rows, N]."""
+    q = np.asarray(q, dtype=np.float32)
+    rows, N, A = q.shape
+    m = np.ones(q.shape, dtype=bool) if avail is None else np.asarray(avail) != 0
+    u = select_words(seed, env_ids, t, N)
+    lo = u & np.uint64(0xFFFFFFFF)
+    if SELECT_MODES[mode] == 0:
+        g = greedy_index(np.where(m, q, np.float32(-np.inf)))
+        explore = ((u >> np.uint64(32)) < np.uint64(eps_q)) & (not greedy_only)
+        n = m.sum(-1)
+        k = ((lo * n.astype(np.uint64)) >> np.uint64(32)).astype(np.int64)
+        kth = (m & (np.cumsum(m, -1) - 1 == k[..., None])).argmax(-1)
+        return np.where(explore & (n > 0), kth, g).astype(np.int64)
+    p = np.where(m, q, np.float32(0.0)).astype(np.float32)
+    g = greedy_index(p)
+    if greedy_only:
+        return g
+    c = np.empty_like(p)
+    with np.errstate(invalid="ignore", over="ignore"):
+        c[..., 0] = p[..., 0]
+        for i in range(1, A):
+            c[..., i] = c[..., i - 1] + p[..., i]                    # float32, in this order
+        s = c[..., -1]
+        ok = np.isfinite(s) & (s > 0)
+        r = (lo >> np.uint64(8)).astype(np.float32) * np.float32(2.0 ** -24)
+        x = (r * s).astype(np.float32)
+        above = c > x[..., None]
+        last_pos = A - 1 - (p > 0)[..., ::-1].argmax(-1)
+    drawn = np.where(above.any(-1), above.argmax(-1), last_pos)
+    return np.where(ok, drawn, g).astype(np.int64)
 
 
 def cell_keys(seed, env_ids, n_cells, stream):

@@ -27,8 +27,9 @@ actions row at step t cover the envs that were running before step t - 1.  The
 MAC gets `bs` as a device LongTensor of length B (ascending running env ids,
 padded with the first one), a form the reference EpisodeBatch / BasicMAC index
 with (episode_buffer.py:186-190); `args.runner_exact_bs` passes the exact-length
-list instead (one host sync per step, for stochastic action selectors whose RNG
-consumption must follow the reference's).
+list instead (one host sync per step, for stochastic torch action selectors whose RNG
+consumption must follow the reference's; mapfx.selectors' device selectors key their random
+words by env and step -- `run` binds them -- and pick the same actions from either form).
 
 `collect()` is a run with no MAC at all: the whole episode loop as one launch
 (mapfx_runner_rollout), the actions from the on-device policy or a given table, the
@@ -303,6 +304,9 @@ class ParallelRunner:
         # terminated.  args.runner_exact_bs = True passes bs[:len(bs)] instead, at the
         # cost of one host sync per step (the count of the previous step's compaction).
         exact_bs = bool(getattr(self.args, "runner_exact_bs", False))
+        # A selector with `bind` (mapfx.selectors) keys its random words by (run, env id,
+        # step): it picks the same actions from the padded and from the exact `bs`.
+        bind = getattr(getattr(self.mac, "action_selector", None), "bind", None)
         k = 0
         max_t = int(r.max_t)
         while k < max_t:
@@ -318,6 +322,8 @@ class ParallelRunner:
                 if int(hc[0]) == 0:   # no env was running before step k - 1: the
                     break             # reference stopped after MAC call k - 1
                 bs = self._bs[:int(hc[0])]
+            if bind is not None:
+                bind(env_ids=bs, t_ep=k, run=self._episode - 1, env_offset=env.env_offset)
             actions = self.mac.select_actions(self.batch, t_ep=k, t_env=self.t_env, bs=bs,
                                               test_mode=test_mode)
             # row j is env bs[j] (j < len(bs) read)
