@@ -17,9 +17,9 @@
  * Same conventions as mapfx.h: caller-owned DEVICE pointers, (row, col) int32
  * positions, LSB-first obstacle bitmaps of mapfx_map_stride(H, W) bytes per env,
  * asynchronous on `stream`, 0 / negative MAPFX_E* return codes, messages from
- * mapfx_last_error().  Not part of this ABI: the visualisation hooks, and the `output`
- * mode's random collision repair (:262-275), which the drop-in env
- * (mapfx/envs/marl_partial.py) runs on the host around these calls.
+ * mapfx_last_error().  Not part of this ABI: the visualisation hooks.  The `output` mode's
+ * collision repair (:262-275) is mapfx_partial_repair below; the drop-in env
+ * (mapfx/envs/marl_partial.py) still runs the reference's own host form by default.
  *
  * Limits: N <= 1024, H <= 1024, W <= 1536, and for a side above 256 the BFS
  * frontier rows must fit LDS: H * ceil(W / 64) * 8 bytes plus the BFS kernel's few
@@ -290,6 +290,67 @@ int mapfx_partial_rollout_fused(const mapfx_partial_t* h);
  * 0..4, first report wins) for the calls that take no mapfx_partial_out
  * (mapfx_runner_rollout, mapfx_runner.h).  NULL (the default): not reported.  Additive. */
 int mapfx_partial_bind_err(mapfx_partial_t* h, int32_t* err);
+
+/* Output mode (`output=True`, :262-275): after the raw step, colliding agents are moved until
+ * no node or edge collision is left (solvers :645-711 and :739-820).  Call it right after
+ * mapfx_partial_step, with the positions the step started from and the actions it read.
+ * Additive exports (the ABI version is unchanged).
+ *
+ * The rule is mapfx.rng.partial_repair (mapfx/rng.py), which this call equals bit for bit.
+ * The reference's: the free-cell test on the PRE-step occupancy, the raw node / edge checks,
+ * the node rounds, then the edge rounds over the RAW pair set, with every quirk of the
+ * solvers' count bookkeeping.  This library's own: each `while` loop is cut at max_rounds
+ * rounds (the reference's can spin for ever: a swap the node repair created is in no raw
+ * pair), and each random.shuffle is a counter-based order.  With splitmix64 and K_* as in
+ * mapfx_action (mapfx.h / mapfx/rng.py), gid = cfg.env_offset + e, t = st->t[e] (the step
+ * count after the step), r the round within its phase from 0:
+ *
+ *   word(site, r, owner, j) = splitmix64(seed ^ gid*K_ENV ^ (uint32)t*K_T ^ owner*K_AGENT
+ *                                        ^ (r*4096 + j)*K_CELL ^ (0x800 + site)*K_STREAM)
+ *
+ * The items in canonical ascending order (agent index; (i, j), i < j, lexicographic; 0..3),
+ * item j keyed (word & ~0xFFFF) | j, processed in ascending key order:
+ *   site 0  the colliding agents of a node round        owner 0
+ *   site 1  these_agents of agent a                      owner a
+ *   site 2  acts_try of agent a                          owner a
+ *   site 3  the pairs of an edge round                   owner 0
+ *   site 4  the members of pair (i, j): (j, i) iff bit 63 of word(4, r, i, j), else (i, j)
+ *
+ * st->pos, st->node (the vector of the last node check) and st->edge (of the last edge check)
+ * are updated in place; rewards, at_goal, goal_cost, total_coll, terminated, done, steps and t
+ * stay those of the raw step, as in the reference (:216-234, 250-258, 291-299).  An env whose
+ * round cap was hit keeps the positions of its last round.  An env with an action outside
+ * 0..4 (the step skipped it) is not repaired: flags 0, nothing else of it written.
+ * With out != NULL the observations of every env (obs, state, avail) are then produced as
+ * mapfx_partial_observe produces them -- which also refreshes pdist / pnbr, stale after a
+ * repair; out->reward is never written.  Asynchronous on `stream`, no allocation, no host
+ * sync (graph-capturable): one launch of partial_repair_kernel (mapfx_last_kernel names it),
+ * one wavefront per env, then the observe launch.
+ * Offered where the wave kernel runs (N <= 64, sides <= 256).  MAPFX_EINVAL before any
+ * launch: a NULL handle, state, args, old_pos, actions or flags; a bad action_dtype;
+ * max_rounds outside 1..16; a handle on which the call is not offered.  E == 0: OK. */
+#define MAPFX_REPAIR_NODE_RAN 1  /* flags: the node phase ran            */
+#define MAPFX_REPAIR_EDGE_RAN 2  /*        the edge phase ran            */
+#define MAPFX_REPAIR_NODE_CAP 4  /*        the node phase hit max_rounds */
+#define MAPFX_REPAIR_EDGE_CAP 8  /*        the edge phase hit max_rounds */
+/* the edge check of the FINAL positions reads above 0.  With bit 3 clear this is a swap the
+ * node phase created on a step whose raw edge count was 0: the reference starts no edge phase
+ * then (:269), so the swap stays, there as here.  st->edge still holds the last check the
+ * rule made. */
+#define MAPFX_REPAIR_SWAP_LEFT 16
+typedef struct mapfx_partial_repair_args {
+  uint64_t seed;
+  const int32_t* old_pos;      /* [E][N][2] positions before the step            */
+  const void* actions;         /* the step's [E][N]                              */
+  int32_t action_dtype;
+  int32_t max_rounds;          /* 1..16 per phase                                */
+  uint8_t* flags;              /* [E] written for every env                      */
+  int32_t* rounds;             /* [E][2] rounds used (node, edge), or NULL       */
+} mapfx_partial_repair_args;
+int mapfx_partial_repair(mapfx_partial_t* h, const mapfx_partial_state* st, const mapfx_partial_repair_args* ra,
+                         const mapfx_partial_out* out, void* stream);
+/* 1: mapfx_partial_repair runs on this handle; 0 otherwise. */
+int mapfx_partial_repair_offered(const mapfx_partial_t* h);
 
 #ifdef __cplusplus
 }

@@ -115,6 +115,16 @@ int mapfx_runner_step(mapfx_partial_t* h, const mapfx_partial_state* st, const m
                       int64_t row_stride, int32_t ts, int32_t* counts_out,
                       const mapfx_episode_rows* rows, void* stream);
 
+/* Output mode (mapfx_partial_repair, mapfx_partial.h): after mapfx_runner_step at ts and the
+ * repair of that step -- whose `out` now holds the observations of the repaired state -- the
+ * obs / state / avail_actions rows at ts + 1 are written again from `out`, with
+ * EpisodeBatch's dtypes, for every env b with rows->filled[b][ts + 1] != 0 (the step has
+ * just written that row from the raw positions); other envs are not touched.  One small
+ * launch; none when ts + 1 == max_t.  MAPFX_EINVAL: a NULL argument, out->obs / state /
+ * avail or rows->filled NULL, ts outside the batch.  Additive export. */
+int mapfx_runner_reobserve(const mapfx_runner_state* rs, const mapfx_partial_out* out, int32_t ts,
+                           const mapfx_episode_rows* rows, void* stream);
+
 /* T runner steps, ts = ts0 .. ts0 + T - 1, of all B envs in one call: the episode loop with
  * no MAC between the steps.  Additive exports (the ABI version is unchanged).
  *

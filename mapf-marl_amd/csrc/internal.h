@@ -88,6 +88,14 @@ int mapfx_partial_rollout_runner(mapfx_partial_t* h, const mapfx_partial_state* 
                                  int action_dtype, const mapfx_partial_policy* pol, const mapfx_runner_acts* ra,
                                  const mapfx_runner_roll* rr, void* stream);
 int mapfx_partial_runner_rollout_offered(const mapfx_partial_t* h, int policy);
+// partial.hip, for repair.hip: the handle's shape (big: the workgroup path, N > 64 or a side
+// > 256) and the state check every mapfx_partial_* entry point makes
+typedef struct mapfx_partial_shape {
+  int32_t H, W, N, E, map_shared, big;
+  long long map_stride, env_offset;
+} mapfx_partial_shape;
+int mapfx_partial_shape_of(const mapfx_partial_t* h, mapfx_partial_shape* s);
+int mapfx_partial_check_state(const mapfx_partial_t* h, const mapfx_partial_state* st);
 
 #ifdef MAPFX_SPLIT_PROBE
 // ---- split protocol probe: libmapfx_probe.so only (mapfx.hip compiled with

@@ -2812,6 +2812,15 @@ int mapfx_partial_observe(mapfx_partial_t* h, const mapfx_partial_state* st,
 
 int mapfx_partial_rollout_fused(const mapfx_partial_t* h) { return h && !h->geo.big ? 1 : 0; }
 
+// internal.h: what repair.hip needs of a handle
+int mapfx_partial_shape_of(const mapfx_partial_t* h, mapfx_partial_shape* s) {
+  if (!h || !s) return perr(MAPFX_EINVAL, "NULL handle");
+  const PGeo& g = h->geo;
+  *s = mapfx_partial_shape{g.H, g.W, g.N, g.E, g.map_shared, g.big, g.map_stride, (long long)h->cfg.env_offset};
+  return MAPFX_OK;
+}
+int mapfx_partial_check_state(const mapfx_partial_t* h, const mapfx_partial_state* st) { return check_state(h, st); }
+
 int mapfx_partial_rollout(mapfx_partial_t* h, const mapfx_partial_state* st, int32_t T, const void* actions,
                           int action_dtype, const mapfx_partial_policy* pol, int32_t autoreset,
                           const mapfx_partial_traj* traj, void* stream) {

@@ -104,6 +104,15 @@ __global__ void runner_actions_kernel(mapfx_runner_state rs, const void* acts, i
   rs.env_actions[b * rs.N + n] = (int8_t)((a < -128 || a > 127) ? -1 : a);
 }
 
+// output mode: the rows at ts + 1 of every env the step just wrote them for (filled != 0),
+// again, from the observations of the repaired state (mapfx_runner_reobserve)
+__global__ void __launch_bounds__(RB) runner_reobserve_kernel(mapfx_runner_state rs, mapfx_partial_out o, int ts,
+                                                              mapfx_episode_rows r) {
+  const int b = blockIdx.x;
+  if (r.filled[(int64_t)b * r.filled_sb + (int64_t)(ts + 1) * r.filled_st] == 0) return;  // uniform per block
+  write_pre(rs, o, r, b, ts + 1);
+}
+
 // receive loop of one step (:125-173) for every env still running
 __global__ void __launch_bounds__(RB) runner_post_kernel(mapfx_runner_state rs, const uint8_t* term,
                                                          mapfx_partial_out o, int ts,
@@ -400,6 +409,18 @@ int mapfx_runner_post(const mapfx_runner_state* rs, const uint8_t* terminated,
   if (rc) return rc;
   return launch_kernel(runner_compact_kernel, dim3(1), dim3(CT), 0, (hipStream_t)stream, nullptr, nullptr,
                        "runner_compact_kernel launch", QUIET, *rs, counts_out, (int32_t*)nullptr);
+}
+
+int mapfx_runner_reobserve(const mapfx_runner_state* rs, const mapfx_partial_out* out, int32_t ts,
+                           const mapfx_episode_rows* rows, void* stream) {
+  int rc = check_rs(rs);
+  if (rc) return rc;
+  if (!out || !rows || !out->obs || !out->state || !out->avail || !rows->filled)
+    return perr(MAPFX_EINVAL, "runner_reobserve: NULL out / rows / filled rows");
+  if (ts < 0 || ts >= rows->max_t) return perr(MAPFX_EINVAL, "runner_reobserve: ts outside the batch");
+  if (rs->B == 0 || ts + 1 == rows->max_t) return MAPFX_OK;  // no row ts + 1: nothing to launch
+  return launch_kernel(runner_reobserve_kernel, dim3(rs->B), dim3(RB), 0, (hipStream_t)stream, nullptr, nullptr,
+                       "runner_reobserve_kernel launch", QUIET, *rs, *out, (int)ts, *rows);
 }
 
 int mapfx_runner_step(mapfx_partial_t* h, const mapfx_partial_state* st, const mapfx_partial_out* out,

@@ -87,6 +87,11 @@ class PPolicy(ctypes.Structure):  # include/mapfx_partial.h mapfx_partial_policy
     _fields_ = [("seed", c_u64), ("eps_q", c_u64), ("t0", c_i32)]
 
 
+class PRepair(ctypes.Structure):  # include/mapfx_partial.h mapfx_partial_repair_args
+    _fields_ = [("seed", c_u64), ("old_pos", c_vp), ("actions", c_vp), ("action_dtype", c_i32),
+                ("max_rounds", c_i32), ("flags", c_vp), ("rounds", c_vp)]
+
+
 class QCfg(ctypes.Structure):  # include/mapfx_primal.h
     _fields_ = [(k, c_i32) for k in ("H", "W", "n_agents", "n_envs", "obs_size", "map_shared",
                                      "diagonal")]
@@ -127,7 +132,8 @@ EXPORTS = ("mapfx_abi_version", "mapfx_last_error", "mapfx_build_id", "mapfx_las
            "mapfx_runner_step", "mapfx_host_ring_alloc", "mapfx_host_ring_free",
            "mapfx_partial_bind_err", "mapfx_runner_rollout", "mapfx_runner_rollout_offered",
            "mapfx_partial_policy_rule", "mapfx_partial_policy_rule_offered",
-           "mapfx_select_actions", "mapfx_select_word")
+           "mapfx_select_actions", "mapfx_select_word",
+           "mapfx_partial_repair", "mapfx_partial_repair_offered", "mapfx_runner_reobserve")
 
 
 class ERows(ctypes.Structure):  # include/mapfx_runner.h mapfx_episode_rows
@@ -213,7 +219,10 @@ def _load():
         "mapfx_runner_post": (c_i32, [P(RState), c_vp, P(POut), c_i32, c_vp, P(ERows), c_vp]),
         "mapfx_runner_step": (c_i32, [c_vp, P(PState), P(POut), P(RState), c_vp, c_i32, c_i64, c_i32,
                                       c_vp, P(ERows), c_vp]),
+        "mapfx_runner_reobserve": (c_i32, [P(RState), P(POut), c_i32, P(ERows), c_vp]),
         "mapfx_partial_bind_err": (c_i32, [c_vp, c_vp]),
+        "mapfx_partial_repair": (c_i32, [c_vp, P(PState), P(PRepair), P(POut), c_vp]),
+        "mapfx_partial_repair_offered": (c_i32, [c_vp]),
         "mapfx_partial_policy_rule": (c_i32, [c_vp, c_i32]),
         "mapfx_partial_policy_rule_offered": (c_i32, [c_vp, c_i32]),
         "mapfx_runner_rollout": (c_i32, [c_vp, P(PState), P(RState), c_i32, c_i32, c_vp, c_i32,

@@ -7,7 +7,9 @@ available actions come from the HIP kernels (mapfx.partial.MarlPartialBatch,
 E = 1).  Observations are float32, the dtype PyMARL's EpisodeBatch stores them
 in.  `output=True` repairs each step's collisions on the host with the reference's
 randomised tries (:262-275, :645-820), then re-observes on the device
-(tests/test_partial_output_mode.py).  Not reproduced (out of scope): rendering / visual
+(tests/test_partial_output_mode.py); with repair="device" the repair is the batch's own
+mapfx_partial_repair instead (counter-based orders, a round cap: mapfx.rng.partial_repair),
+one step call and one pull per step.  Not reproduced (out of scope): rendering / visual
 json export.
 """
 from __future__ import annotations
@@ -32,9 +34,14 @@ class MARL_PARTIAL_ENV(MultiAgentEnv):
                  episode_limit=100, seed=None, render='human', move_reward=-0.01, stay_reward=-0.02,
                  stay_goal_reward=0, node_collide_reward=-1, edge_collide_reward=-1,
                  env_collide_reward=-1, complete_reward=1000, complete_fac=1.5, debug=False,
-                 visual=False, gamma=0.99, output=False, device=None):
+                 visual=False, gamma=0.99, output=False, device=None, repair="host"):
         assert os.path.exists(grid_file_path)                                    # :54
+        if repair not in ("host", "device"):
+            raise ValueError("repair must be 'host' or 'device', not %r" % (repair,))
         self._output_mode = bool(output)   # :58 (collision repair after the step, :262-275)
+        # "device": the repair is mapfx_partial_repair inside the batch's step (one step call,
+        # one pull; the counter-based orders of rng.partial_repair instead of random.shuffle)
+        self._device_repair = self._output_mode and repair == "device"
         self._grid_file_path = grid_file_path
         self._agent_path = agents_path
         self._render_mode = render
@@ -62,6 +69,7 @@ class MARL_PARTIAL_ENV(MultiAgentEnv):
         self._agent_goal_pos = [(-1, -1) for _ in self.agents]
         self.__setup_grid()                                                      # :107
         self.__setup_agent()                                                     # :108
+        self._repair_seed = random.randint(0, 2 ** 63 - 1) if self._device_repair else 0
         self._batch = None
         self._step_count = None
         self._terminated = False
@@ -90,7 +98,9 @@ class MARL_PARTIAL_ENV(MultiAgentEnv):
         goals = np.array([self._agent_goal_pos], dtype=np.int32)
         if self._batch is None:
             self._batch = MarlPartialBatch(init, goals, grids=self._grid[None],
-                                           device=self._device, packed=True, **self._params)
+                                           device=self._device, packed=True,
+                                           output=self._device_repair,
+                                           repair_seed=self._repair_seed, **self._params)
             self._host_flat, self._host = self._batch.host_mirror()
             self._act_host = torch.empty((1, self._n_agents), dtype=torch.int8, pin_memory=True)
             self._act_dev = torch.empty((1, self._n_agents), dtype=torch.int8,
@@ -137,7 +147,7 @@ class MARL_PARTIAL_ENV(MultiAgentEnv):
         R = float(h["reward"][0])
         self._step_count += 1
         self._terminated = bool(h["terminated"][0])
-        if self._output_mode:
+        if self._output_mode and not self._device_repair:
             self._repair(old_pos, list(agents_action))
         return R, self._terminated, {'_step_count': self._step_count}
 

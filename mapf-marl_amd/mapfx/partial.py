@@ -30,7 +30,7 @@ class MarlPartialBatch(DeviceBatch):
     (nonzero = obstacle) or `bits` [E|1, map_stride]; init_pos / goals [E, N, 2]."""
 
     def __init__(self, init_pos, goals, grids=None, bits=None, hw=None, device=None, env_offset=0,
-                 packed=False, **params):
+                 packed=False, *, output=False, repair_seed=0, repair_rounds=16, **params):
         unknown = set(params) - set(DEFAULTS)
         if unknown:
             raise TypeError("unknown MARL_PARTIAL_ENV parameters: %s" % sorted(unknown))
@@ -102,6 +102,21 @@ class MarlPartialBatch(DeviceBatch):
                                   err=ptr(self.err))
         self._scen = None   # set_scenarios: the device scenario draw's table and counters
         self._traj_cache = {}   # rollout: (T, obs, policy mode) -> its trajectory tensors
+        # output mode (:262-275): every step is followed by mapfx_partial_repair
+        self.output = bool(output)
+        if self.output:
+            if not lib.mapfx_partial_repair_offered(self._h):
+                raise ValueError("output mode's device repair is not offered for n_agents = %d on a "
+                                 "%d x %d map (it needs n_agents <= 64 and sides <= 256)"
+                                 % (self.N, self.H, self.W))
+            if not 1 <= int(repair_rounds) <= 16:
+                raise ValueError("repair_rounds must be in 1..16")
+            self.repair_flags = z((E,), torch.uint8)
+            self.repair_rounds_used = z((E, 2), torch.int32)
+            self._old_pos = z((E, N, 2), torch.int32)
+            self._repair = _abi.PRepair(seed=u64(repair_seed), old_pos=ptr(self._old_pos), actions=None,
+                                        action_dtype=MAPFX_I8, max_rounds=int(repair_rounds),
+                                        flags=ptr(self.repair_flags), rounds=ptr(self.repair_rounds_used))
         self.compute_goal_dist()
 
     # ------------------------------------------------------------------ API
@@ -173,8 +188,15 @@ class MarlPartialBatch(DeviceBatch):
     def step(self, actions):
         """One step of all E envs (:165-310).  actions: [E, N] int8/int32/int64."""
         a, dt = as_actions(actions, self.device, (self.E, self.N))
+        if self.output:
+            self._old_pos.copy_(self.pos)
         check(self._call(lib.mapfx_partial_step, self._h, ctypes.byref(self._state), a.data_ptr(),
                          dt, ctypes.byref(self._out)), "mapfx_partial_step")
+        if self.output:   # the collision repair, then the observations of the repaired state
+            self._repair.actions, self._repair.action_dtype = a.data_ptr(), dt
+            check(self._call(lib.mapfx_partial_repair, self._h, ctypes.byref(self._state),
+                             ctypes.byref(self._repair), ctypes.byref(self._obs_out)),
+                  "mapfx_partial_repair")
         return self.out
 
     TRAJ_KEYS = ("reward", "obs", "state", "avail", "pos", "terminated", "actions")
@@ -229,6 +251,9 @@ class MarlPartialBatch(DeviceBatch):
         pos and terminated after that step, actions in policy mode -- allocated once per
         (T, obs, mode) and reused, or the caller's own `out` (the same keys; a missing one
         is not produced)."""
+        if self.output:
+            raise ValueError("rollout is not offered in output mode (the repair is not fused "
+                             "into the rollout kernels): use step()")
         self.set_policy_rule(policy)
         policy = actions is None
         if policy:

@@ -193,6 +193,15 @@ def runner_policy_seed(seed, run):
                           ^ _mul(np.uint64(int(run) & 0xFFFFFFFFFFFFFFFF), K_T)))
 
 
+def runner_repair_seed(seed, run):
+    """The repair seed of run number `run` of ParallelRunner.run with runner_device_repair:
+    splitmix64(seed ^ run * K_T ^ STREAM_REPAIR * K_STREAM) -- `runner_policy_seed`'s
+    derivation on the repair's stream, so a run can be replayed from its number."""
+    return int(splitmix64(np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF)
+                          ^ _mul(np.uint64(int(run) & 0xFFFFFFFFFFFFFFFF), K_T)
+                          ^ _mul(np.uint64(0x800), K_STREAM)))
+
+
 def select_words(seed, env_ids, t, n_agents):
     """The selection stream's words, uint64 [len(env_ids), n_agents]:
     splitmix64(seed ^ gid*K_ENV ^ (uint32)t*K_T ^ a*K_AGENT ^ STREAM_SELECT*K_STREAM)
@@ -305,3 +314,257 @@ def scen_draw(seed, env_ids, episodes, n_lines, n_agents):
         s = (splitmix64(base[e] ^ _mul(j, K_CELL) ^ sl) & ~np.uint64(0xFFFF)) | j
         line[e] = (np.sort(s)[:N] & np.uint64(0xFFFF)).astype(np.int32)
     return file, line
+
+
+# Stream of output mode's collision repair (mapfx_partial_repair, csrc/repair.hip): site s of
+# the table below draws from stream STREAM_REPAIR + s
+STREAM_REPAIR = 0x800
+REPAIR_MAX_ROUNDS = 16
+# mapfx_partial_repair's flags byte (include/mapfx_partial.h MAPFX_REPAIR_*)
+REPAIR_NODE_RAN, REPAIR_EDGE_RAN, REPAIR_NODE_CAP, REPAIR_EDGE_CAP = 1, 2, 4, 8
+REPAIR_SWAP_LEFT = 16   # the edge check of the final positions reads above 0
+# what partial_repair(counters=True) counts, in this order: a colliding agent sent back to its
+# old cell, moved by one of `these_acts`, moved by one of `acts_try`; a swapping agent that
+# side-stepped, that backed up, a pair put back on its old cells
+REPAIR_COUNTERS = ("node_back", "node_these", "node_try", "edge_side", "edge_back", "edge_put")
+_REPAIR_DELTA = ((-1, 0), (1, 0), (0, -1), (0, 1))           # marl_partial.py:617-643, acts 0..3
+_REPAIR_SIDE = ((2, 3), (3, 2), (0, 1), (1, 0))              # :775 try_map
+_REPAIR_BACK = (1, 0, 3, 2)                                  # :776
+
+
+def repair_word(seed, gid, t, site, r, owner, j):
+    """splitmix64(seed ^ gid*K_ENV ^ (uint32)t*K_T ^ owner*K_AGENT ^ (r*4096 + j)*K_CELL ^
+    (STREAM_REPAIR + site)*K_STREAM): the word of item j of `site` in round r (per phase, from
+    0) of the repair of global env `gid` at step count t."""
+    m = 0xFFFFFFFFFFFFFFFF                       # (plain Python integers: one word at a time)
+    x = (int(seed) ^ int(gid) * int(K_ENV) ^ (int(t) & 0xFFFFFFFF) * int(K_T) ^ int(owner) * int(K_AGENT)
+         ^ (int(r) * 4096 + int(j)) * int(K_CELL) ^ (STREAM_REPAIR + int(site)) * int(K_STREAM)) & m
+    x = (x + 0x9E3779B97F4A7C15) & m
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & m
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & m
+    return x ^ (x >> 31)
+
+
+def repair_order(seed, gid, t):
+    """The counter-based `order(site, r, owner, items)` of partial_repair for one env-step: the
+    items in canonical ascending order, item j keyed (repair_word(.., site, r, owner, j) &
+    ~0xFFFF) | j, returned in ascending key order.  Site 4 (the two members (i, j) of a pair):
+    (j, i) iff bit 63 of repair_word(.., 4, r, i, j) is set."""
+    def order(site, r, owner, items):
+        items = sorted(items)
+        if site == 4:
+            i, j = items
+            return [j, i] if repair_word(seed, gid, t, 4, r, i, j) >> 63 else [i, j]
+        keys = [(repair_word(seed, gid, t, site, r, owner, j) & ~0xFFFF) | j for j in range(len(items))]
+        return [items[k & 0xFFFF] for k in sorted(keys)]
+    return order
+
+
+def _repair_check_node(pos):
+    """marl_partial.py:713-737 -> (count, 0/1 vector)."""
+    n = {}
+    for p in pos:
+        n[p] = n.get(p, 0) + 1
+    vec = [1 if n[p] > 1 else 0 for p in pos]
+    return sum(vec), vec
+
+
+def _repair_check_edge(old, new):
+    """marl_partial.py:822-857 -> (count, vector, set of sorted pairs)."""
+    vec, pairs = [0] * len(new), set()
+    for i, (io, inew) in enumerate(zip(old, new)):
+        if io == inew:
+            continue
+        for j, jo in enumerate(old):
+            if j != i and jo == inew and new[j] == io:
+                vec[i] += 1
+                pairs.add(tuple(sorted([i, j])))
+    return sum(vec), vec, pairs
+
+
+def partial_repair_env(old, new, acts, grid, t, gid, seed=0, max_rounds=REPAIR_MAX_ROUNDS, order=None,
+                       counters=None):
+    """Output mode's collision repair of ONE env-step (MARL-curve-main/src/envs/marl_partial.py
+    :262-275 with the solvers :645-711 and :739-820), the definition of mapfx_partial_repair
+    (include/mapfx_partial.h).  The reference's control flow, quirks included; its two `while`
+    loops are cut at `max_rounds` rounds each and every random.shuffle is `order(site, r,
+    owner, items)` -- by default `repair_order(seed, gid, t)`.
+
+    old / new: the N cells (row, col) before the step and the raw ones after it; acts: the
+    step's actions (0..4); grid [H, W], nonzero = obstacle; t: the env's step count after the
+    step.  A cell is free iff it is on the grid and is no obstacle or held an agent before the
+    step (grid + counts(old) != -1, :504-522).
+
+    Returns (pos, node_vec, edge_vec, flags, (node rounds, edge rounds)): the vectors are those
+    of the last check of each kind (the raw one where the phase did not run); flags bit 4
+    (REPAIR_SWAP_LEFT) says that the edge check of the final positions reads above 0.  `counters`, a
+    dict, gets REPAIR_COUNTERS added up."""
+    if not 1 <= int(max_rounds) <= REPAIR_MAX_ROUNDS:
+        raise ValueError("max_rounds must be in 1..%d" % REPAIR_MAX_ROUNDS)
+    grid = np.asarray(grid)
+    H, W = grid.shape
+    old = [(int(p[0]), int(p[1])) for p in old]
+    new = [(int(p[0]), int(p[1])) for p in new]
+    acts = [int(a) for a in acts]
+    n = len(new)
+    if order is None:
+        order = repair_order(seed, gid, t)
+    cnt_br = counters if counters is not None else {}
+    held = set(old)
+
+    def bump(k):
+        cnt_br[k] = cnt_br.get(k, 0) + 1
+
+    def free(p):
+        return 0 <= p[0] < H and 0 <= p[1] < W and (grid[p] == 0 or p in held)
+
+    def move(p, a):
+        return (p[0] + _REPAIR_DELTA[a][0], p[1] + _REPAIR_DELTA[a][1])
+
+    def counts():
+        c = {}
+        for p in new:
+            c[p] = c.get(p, 0) + 1
+        return c
+
+    def solve_node(r, node_vec):                                                   # :645-711
+        col = order(0, r, 0, [i for i in range(n) if node_vec[i] > 0])
+        cnt = counts()
+        for a in col:
+            a_pos = new[a]
+            if cnt.get(a_pos, 0) <= 1:
+                continue
+            o = old[a]
+            if cnt.get(o, 0) <= 0:
+                cnt[a_pos] = cnt.get(a_pos, 0) - 1
+                new[a] = o
+                cnt[o] = cnt.get(o, 0) + 1
+                bump("node_back")
+                continue
+            these = order(1, r, a, [i for i in range(n) if new[i] == o])
+            solved = False
+            for act in [acts[i] for i in these]:
+                if act == acts[a]:
+                    continue
+                if act == 4:                       # __agent_step: a stay is the old cell itself
+                    p = o
+                else:
+                    p = move(o, act)
+                    if not free(p):
+                        continue
+                if cnt.get(p, 0) <= 0:
+                    cnt[a_pos] = cnt.get(a_pos, 0) - 1
+                    new[a] = p
+                    cnt[p] = cnt.get(p, 0) + 1
+                    bump("node_these")
+                    solved = True
+                    break
+            if solved:
+                continue
+            for act in order(2, r, a, [0, 1, 2, 3]):
+                p = move(o, act)
+                if act == acts[a] or not free(p):
+                    continue
+                if cnt.get(p, 0) <= 0:
+                    cnt[o] = cnt.get(o, 0) - 1     # the OLD cell, not a_pos (:706)
+                    new[a] = p
+                    cnt[p] = cnt.get(p, 0) + 1
+                    bump("node_try")
+                    break
+
+    def solve_edge(r, pairs):                                                      # :739-820
+        cnt = counts()
+        for pair in order(3, r, 0, pairs):
+            pair = order(4, r, min(pair), [pair[0], pair[1]])
+            solved = False
+            a_pos = None
+            for a in pair:
+                a_pos = new[a]
+                for act in _REPAIR_SIDE[acts[a]]:
+                    p = move(old[a], act)
+                    if free(p) and cnt.get(p, 0) <= 0:
+                        cnt[a_pos] = cnt.get(a_pos, 0) - 1
+                        new[a] = p
+                        cnt[p] = cnt.get(p, 0) + 1
+                        bump("edge_side")
+                        solved = True
+                        break
+                if solved:
+                    break
+            if solved:
+                continue
+            for a in pair:
+                p = move(old[a], _REPAIR_BACK[acts[a]])
+                if free(p) and cnt.get(p, 0) <= 0:
+                    cnt[a_pos] = cnt.get(a_pos, 0) - 1   # a_pos as the loop above left it (:807)
+                    new[a] = p
+                    cnt[p] = cnt.get(p, 0) + 1
+                    bump("edge_back")
+                    solved = True
+            if solved:
+                continue
+            bump("edge_put")
+            for a in pair:
+                new[a] = old[a]
+
+    n_node, node_vec = _repair_check_node(new)                                     # :236
+    n_edge, edge_vec, pairs = _repair_check_edge(old, new)                         # :238
+    flags, rounds = 0, [0, 0]
+    if n_node > 0:                                                                 # :263-268
+        flags |= REPAIR_NODE_RAN
+        while n_node > 0 and rounds[0] < max_rounds:
+            solve_node(rounds[0], node_vec)
+            n_node, node_vec = _repair_check_node(new)
+            rounds[0] += 1
+        if n_node > 0:
+            flags |= REPAIR_NODE_CAP
+    if n_edge > 0 and not flags & REPAIR_NODE_CAP:                                 # :269-275
+        flags |= REPAIR_EDGE_RAN
+        while n_edge > 0 and rounds[1] < max_rounds:
+            solve_edge(rounds[1], pairs)                 # always the RAW pair set (:246, :272)
+            n_edge, edge_vec, _ = _repair_check_edge(old, new)
+            rounds[1] += 1
+        if n_edge > 0:
+            flags |= REPAIR_EDGE_CAP
+    # a swap on the final positions (the edge vector returned stays that of the last check the
+    # reference makes): with no cap hit, one the node phase created on a step whose raw edge
+    # count was 0, for which the reference starts no edge phase
+    if flags and _repair_check_edge(old, new)[0] > 0:
+        flags |= REPAIR_SWAP_LEFT
+    return new, node_vec, edge_vec, flags, tuple(rounds)
+
+
+def partial_repair(old, new, acts, grid, t, seed=0, env_offset=0, max_rounds=REPAIR_MAX_ROUNDS, order=None,
+                   counters=False):
+    """`partial_repair_env` over a batch: what mapfx_partial_repair computes, bit for bit.
+
+    old / new [E, N, 2], acts [E, N], grid [H, W] or [E | 1, H, W] (nonzero = obstacle), t one
+    step count or one per env; env e is global env env_offset + e.  An env with an action
+    outside 0..4 (its step was skipped) is not repaired: pos = new, flags 0, zero vectors and
+    skipped[e] set (the device writes nothing of it but the flags byte).  `order`, when given,
+    replaces the counter-based order of every env (see partial_repair_env).
+
+    Returns a dict: pos int32 [E, N, 2], node uint8 [E, N], edge int32 [E, N], flags uint8 [E],
+    rounds int32 [E, 2], skipped bool [E]; with counters=True also counters, int64
+    [len(REPAIR_COUNTERS)]."""
+    old = np.asarray(old, dtype=np.int64)
+    new = np.asarray(new, dtype=np.int64)
+    acts = np.asarray(acts, dtype=np.int64)
+    E, N = acts.shape
+    grid = np.asarray(grid)
+    if grid.ndim == 2:
+        grid = grid[None]
+    tt = np.broadcast_to(np.asarray(t, dtype=np.int64), (E,))
+    res = dict(pos=new.astype(np.int32), node=np.zeros((E, N), np.uint8), edge=np.zeros((E, N), np.int32),
+               flags=np.zeros((E,), np.uint8), rounds=np.zeros((E, 2), np.int32), skipped=np.zeros((E,), bool))
+    cnt = {}
+    for e in range(E):
+        if ((acts[e] < 0) | (acts[e] > 4)).any():
+            res["skipped"][e] = True
+            continue
+        pos, nv, ev, fl, rd = partial_repair_env(old[e], new[e], acts[e], grid[e if grid.shape[0] > 1 else 0],
+                                                 int(tt[e]), env_offset + e, seed, max_rounds, order, cnt)
+        res["pos"][e], res["node"][e], res["edge"][e], res["flags"][e], res["rounds"][e] = pos, nv, ev, fl, rd
+    if counters:
+        res["counters"] = np.array([cnt.get(k, 0) for k in REPAIR_COUNTERS], dtype=np.int64)
+    return res

@@ -31,6 +31,11 @@ list instead (one host sync per step, for stochastic torch action selectors whos
 consumption must follow the reference's; mapfx.selectors' device selectors key their random
 words by env and step -- `run` binds them -- and pick the same actions from either form).
 
+`args.runner_device_repair = True` with `env_args["output"]` (default: `output` is dropped)
+turns on output mode: every step of `run()` is followed by the device collision repair
+(mapfx_partial_repair, seed rng.runner_repair_seed(args.seed, run)) and the rows at ts + 1
+are rewritten from the repaired state (mapfx_runner_reobserve); `collect()` then raises.
+
 `collect()` is a run with no MAC at all: the whole episode loop as one launch
 (mapfx_runner_rollout), the actions from the on-device policy or a given table, the
 batch, t_env and the stats as `run()` leaves them.
@@ -60,7 +65,7 @@ from ._base import DTYPES as _ADT    # noqa: F401  (tools/runner_host_probe.py r
 from ._base import as_actions
 from .maps import draw_scen, load_map, load_scen_table, read_scen
 from .partial import MarlPartialBatch
-from .rng import runner_policy_seed
+from .rng import runner_policy_seed, runner_repair_seed
 
 _ROW_DTYPES = {"obs": torch.float32, "state": torch.float32, "avail_actions": torch.int32,
                "actions": torch.int64, "actions_onehot": torch.float32, "reward": torch.float32,
@@ -99,6 +104,11 @@ class ParallelRunner:
         ea = dict(args.env_args)
         self.n_agents = int(ea.pop("n_agents", 4))
         grid_path, self.agents_path = ea.pop("grid_file_path"), ea.pop("agents_path")
+        # args.runner_device_repair (default False: `output` is dropped, as ever): with
+        # env_args["output"] every step of run() is followed by the device collision repair
+        # (mapfx_partial_repair) and the rows at ts + 1 are written again from the repaired
+        # state (mapfx_runner_reobserve)
+        self._device_repair = bool(getattr(args, "runner_device_repair", False)) and bool(ea.get("output"))
         for k in ("seed", "render", "debug", "visual", "output"):
             ea.pop(k, None)
         dev = torch.device(getattr(args, "device", "cuda"))
@@ -163,6 +173,23 @@ class ParallelRunner:
         host = np.ctypeslib.as_array(ctypes.cast(hp, ctypes.POINTER(ctypes.c_int32)),
                                      shape=(_RING, 2))
         self._ring = [(torch.cuda.Event(), host[i], dp.value + 8 * i) for i in range(_RING)]
+        if self._device_repair:
+            if not lib.mapfx_partial_repair_offered(self.env._h):
+                raise ValueError("runner_device_repair needs n_agents <= 64 and map sides <= 256")
+            # the step's separate-kernel form (no bs_inv): its actions pass leaves every env's
+            # actions in env_actions, which the repair then reads as the step did
+            self._rs_repair = _abi.RState(B=B, N=N, D=self.env.obs_dim, alive=ptr(self._alive),
+                                          alive_prev=ptr(self._alive_prev), bs=ptr(self._bs),
+                                          counts=ptr(self._counts), ep_return=ptr(self._ep_return),
+                                          ep_length=ptr(self._ep_length), env_steps=ptr(self._env_steps),
+                                          env_actions=ptr(self._env_actions), bs_inv=None)
+            self._old_pos = z((B, N, 2), torch.int32)
+            self.repair_flags = z((B,), torch.uint8)
+            self.repair_rounds_used = z((B, 2), torch.int32)
+            self._repair = _abi.PRepair(seed=0, old_pos=ptr(self._old_pos), actions=ptr(self._env_actions),
+                                        action_dtype=_abi.MAPFX_I8,
+                                        max_rounds=int(getattr(args, "runner_repair_rounds", 16)),
+                                        flags=ptr(self.repair_flags), rounds=ptr(self.repair_rounds_used))
         self.t = 0
         self.t_env = 0
         self.train_returns = []
@@ -296,6 +323,13 @@ class ParallelRunner:
         r, rs, env = self._erows, ctypes.byref(self._rs), self.env
         stream = torch.cuda.current_stream(self.device)
         sh = stream.cuda_stream
+        repair = self._device_repair
+        if repair:
+            rs = ctypes.byref(self._rs_repair)
+            base = int(getattr(self.args, "seed", 0) or 0)
+            self._repair.seed = runner_repair_seed(base, self._episode - 1)
+            rep_args = (env._h, ctypes.byref(env._state), ctypes.byref(self._repair),
+                        ctypes.byref(env._obs_out), sh)
         fixed = (env._h, ctypes.byref(env._state), ctypes.byref(env._out), rs)
         step = lib.mapfx_runner_step
         # The MAC gets `bs` padded to B (no host sync per step); a stochastic selector
@@ -329,9 +363,15 @@ class ParallelRunner:
             # row j is env bs[j] (j < len(bs) read)
             a, adt = as_actions(actions.reshape(-1, self.n_agents), self.device)
             ev, _, dslot = self._ring[k % _RING]
+            if repair:
+                self._old_pos.copy_(env.pos)
             rc = step(*fixed, a.data_ptr(), adt, a.stride(0), k, dslot, ctypes.byref(r), sh)
             if rc:
                 check(rc, "mapfx_runner_step")
+            if repair:
+                check(lib.mapfx_partial_repair(*rep_args), "mapfx_partial_repair")
+                check(lib.mapfx_runner_reobserve(rs, ctypes.byref(env._obs_out), k, ctypes.byref(r), sh),
+                      "mapfx_runner_reobserve")
             ev.record(stream)
             k += 1
         self.t = k
@@ -352,6 +392,9 @@ class ParallelRunner:
         the run's totals.  ValueError where the fused call is not offered (N > 64 or a side
         > 256; the policy also needs H * W <= 32767): use run() with a MAC there."""
         env = self.env
+        if self._device_repair:
+            raise ValueError("collect: the one-launch episode loop has no collision repair; with "
+                             "runner_device_repair and output use run()")
         env.set_policy_rule(policy)
         policy = actions is None
         if not lib.mapfx_runner_rollout_offered(env._h, 1 if policy else 0):
