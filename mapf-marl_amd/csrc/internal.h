@@ -11,15 +11,11 @@ extern "C" {
 int mapfx_internal_error(int code, const char* msg);
 // records the host stub of the kernel the calling thread just launched (mapfx_last_kernel)
 void mapfx_note_kernel(const void* fn);
-// partial.hip: mapfx_partial_step with the observation rows written to an EpisodeBatch
-// time row (obs_rows + e * obs_env_stride floats, only envs with obs_mask[e] != 0)
-int mapfx_partial_step_rows(mapfx_partial_t* h, const mapfx_partial_state* st, const void* actions,
-                            int action_dtype, const mapfx_partial_out* out, float* obs_rows,
-                            long long obs_env_stride, const uint8_t* obs_mask, void* stream);
-// The runner's fused step: env e's actions are row act_row[e] (act_row_stride elements
-// apart) of `actions`, stay when act_row[e] < 0; the env's actions / one-hot EpisodeBatch
-// rows at ts are written where act_row[e] >= 0 (ep_actions / ep_onehot may be NULL).
-// obs_rows NULL: observations go to out->obs.
+// The runner's fused step (partial.hip): env e's actions are row act_row[e] (act_row_stride
+// elements apart) of `actions`, stay when act_row[e] < 0; the env's actions / one-hot
+// EpisodeBatch rows at ts are written where act_row[e] >= 0 (ep_actions / ep_onehot may be
+// NULL).  The observation rows go to an EpisodeBatch time row (obs_rows + e * obs_env_stride
+// floats, only envs with obs_mask[e] != 0); obs_rows NULL: to out->obs.
 typedef struct mapfx_runner_acts {
   const int32_t* act_row;
   long long act_row_stride;
@@ -151,7 +147,7 @@ int mapfx_split_probe_read(mapfx_split_probe_trace* out);
 #ifdef __cplusplus
 }
 
-// ---- helpers shared by the four translation units: one definition each ----
+// ---- helpers shared by the five translation units: one definition each ----
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 #include <stdio.h>

@@ -154,7 +154,7 @@ struct PArgs {
   uint8_t* avail;
   int32_t* err;
   const double* bonus_lut;  // (complete / gamma ** (limit - t)) * fac, t = 0 .. bonus_len-1
-  // runner fusion (mapfx_partial_step_rows): observation rows go to obs_rows + e *
+  // runner fusion (mapfx_partial_step_runner): observation rows go to obs_rows + e *
   // obs_env_stride (an EpisodeBatch time row) for the envs with obs_mask[e] != 0,
   // instead of the contiguous `obs`
   float* obs_rows;
@@ -2204,125 +2204,155 @@ void (*pick_wg(int win, int apl))(PGeo, PArgs) {
 
 int wg_apl(const PGeo& g) { return (g.N + WG_THREADS - 1) / WG_THREADS; }
 
+// ---- The wave kernels' instance table: the one place that names their instances. ----
+// Five families share the shapes: partial_kernel (STEP, flag RUN: the runner's fused step)
+// and the four rollouts (flag OBS: the observation rows are built).  A shape is a fast one,
+// <WIN, 5, LF, GDE, flag> with the table width GDE (1 u8 / 2 int16 / 0 read at run time), or
+// the window's generic <WIN, 0, 0, 0, true>.  Without the rows a rollout's window and K play
+// no part: <0, 5, LF, GDE, false> per fast lane group, and the generic <0, 0, 0, 0, false>.
+enum Family { STEP, ROLL, PIBT_ROLL, RUN_ROLL, PIBT_RUN_ROLL };
+
+#define FAST_SHAPES(X) X(5, 16) X(5, 8) X(5, 32) X(3, 16) X(7, 16)  // (WIN, LF), at K = 5
+#define GENERIC_WINDOWS(X) X(0) X(1) X(3) X(5) X(7) X(9)
+
+// What differs per family.  gde[flag][table width] is the GDE of a fast shape's instance:
+// the pibt rule has none for int32 tables (it is not offered there); the runner's rollouts
+// take the generic window instance for them with the rows, and read the width at run time
+// without.
+constexpr int GENERIC = -1, NONE = -2;  // (NONE: nullptr)
+struct FamilyTraits {
+  bool flag_is_obs;  // the flag is OBS (a rollout), not RUN
+  int gde[2][3];
+};
+constexpr FamilyTraits FAMILY[] = {  // (indexed by Family)
+    /* STEP          */ {false, {{0, 1, 2}, {0, 1, 2}}},
+    /* ROLL          */ {true, {{0, 1, 2}, {0, 1, 2}}},
+    /* PIBT_ROLL     */ {true, {{NONE, 1, 2}, {NONE, 1, 2}}},
+    /* RUN_ROLL      */ {true, {{0, 0, 0}, {GENERIC, 1, 2}}},
+    /* PIBT_RUN_ROLL */ {true, {{0, 0, 0}, {GENERIC, 1, 2}}},
+};
+constexpr bool offers(Family f, bool flag, int gde) {
+  for (int v : FAMILY[f].gde[flag])
+    if (v == gde) return true;
+  return false;
+}
+
 using PartialFn = void (*)(PGeo, PArgs);
-
-// the fast-path instance: table width (tw: 1 u8 / 2 int16 / 0 run time) x runner fusion
-template <int WIN, int LF>
-PartialFn pick_fast(int tw, bool run) {
-  if (run) return tw == 1 ? partial_kernel<WIN, 5, LF, 1, true> : tw == 2 ? partial_kernel<WIN, 5, LF, 2, true>
-                                                                          : partial_kernel<WIN, 5, LF, 0, true>;
-  return tw == 1 ? partial_kernel<WIN, 5, LF, 1, false> : tw == 2 ? partial_kernel<WIN, 5, LF, 2, false>
-                                                                  : partial_kernel<WIN, 5, LF, 0, false>;
-}
-
-// The one place that names partial_kernel's instances: launch() asks it for the launch's,
-// mapfx_partial_create walks its whole domain (PICK_*) to raise their dynamic-LDS limit.
-// nullptr: no instance has this window.
-constexpr int PICK_WIN[] = {0, 1, 3, 5, 7, 9}, PICK_K[] = {5, 0}, PICK_L[] = {8, 16, 32, 64}, PICK_TW[] = {0, 1, 2};
-PartialFn pick(int win, int K, int L, int tw, bool run) {
-  if (K == 5 && win == 5 && L == 16) return pick_fast<5, 16>(tw, run);
-  if (K == 5 && win == 5 && L == 8) return pick_fast<5, 8>(tw, run);
-  if (K == 5 && win == 5 && L == 32) return pick_fast<5, 32>(tw, run);
-  if (K == 5 && win == 3 && L == 16) return pick_fast<3, 16>(tw, run);
-  if (K == 5 && win == 7 && L == 16) return pick_fast<7, 16>(tw, run);
-  switch (win) {
-    case 0: return partial_kernel<0, 0, 0>;
-    case 1: return partial_kernel<1, 0, 0>;
-    case 3: return partial_kernel<3, 0, 0>;
-    case 5: return partial_kernel<5, 0, 0>;
-    case 7: return partial_kernel<7, 0, 0>;
-    case 9: return partial_kernel<9, 0, 0>;
-  }
-  return nullptr;
-}
-
-// partial_rollout_kernel's instances: with the rows one per partial_kernel shape (the 15
-// fast ones, the six generic windows); without them the window and K play no part: one per
-// fast lane group and table width, and one generic.
 using RolloutFn = void (*)(PGeo, PArgs, RArgs);
-// (RULE: MAPFX_POLICY_PIBT has instances of its own -- partial_pibt_rollout_kernel -- of the
-// shapes policy mode is offered on: none for int32 tables alone)
-template <int RULE, int WIN, int KF, int LF, int GDE, bool OBS>
-RolloutFn roll_inst() {
-  if constexpr (RULE == MAPFX_POLICY_PIBT) return partial_pibt_rollout_kernel<WIN, KF, LF, GDE, OBS>;
-  else return partial_rollout_kernel<WIN, KF, LF, GDE, OBS>;
-}
-template <int RULE, int WIN, int LF, bool OBS>
-RolloutFn pick_roll_fast(int tw) {
-  if (tw == 1) return roll_inst<RULE, WIN, 5, LF, 1, OBS>();
-  if (tw == 2) return roll_inst<RULE, WIN, 5, LF, 2, OBS>();
-  if constexpr (RULE == MAPFX_POLICY_PIBT) return nullptr;
-  else return roll_inst<RULE, WIN, 5, LF, 0, OBS>();
-}
-template <int RULE = MAPFX_POLICY_DESCENT>
-RolloutFn pick_roll(int win, int K, int L, int tw, bool obs) {
-  if (!obs) {
-    if (L == 8) return pick_roll_fast<RULE, 0, 8, false>(tw);
-    if (L == 16) return pick_roll_fast<RULE, 0, 16, false>(tw);
-    if (L == 32) return pick_roll_fast<RULE, 0, 32, false>(tw);
-    return roll_inst<RULE, 0, 0, 0, 0, false>();
-  }
-  if (K == 5 && win == 5 && L == 16) return pick_roll_fast<RULE, 5, 16, true>(tw);
-  if (K == 5 && win == 5 && L == 8) return pick_roll_fast<RULE, 5, 8, true>(tw);
-  if (K == 5 && win == 5 && L == 32) return pick_roll_fast<RULE, 5, 32, true>(tw);
-  if (K == 5 && win == 3 && L == 16) return pick_roll_fast<RULE, 3, 16, true>(tw);
-  if (K == 5 && win == 7 && L == 16) return pick_roll_fast<RULE, 7, 16, true>(tw);
-  switch (win) {
-    case 0: return roll_inst<RULE, 0, 0, 0, 0, true>();
-    case 1: return roll_inst<RULE, 1, 0, 0, 0, true>();
-    case 3: return roll_inst<RULE, 3, 0, 0, 0, true>();
-    case 5: return roll_inst<RULE, 5, 0, 0, 0, true>();
-    case 7: return roll_inst<RULE, 7, 0, 0, 0, true>();
-    case 9: return roll_inst<RULE, 9, 0, 0, 0, true>();
-  }
-  return nullptr;
-}
-RolloutFn pick_roll_rule(int rule, int win, int K, int L, int tw, bool obs) {
-  return rule == MAPFX_POLICY_PIBT ? pick_roll<MAPFX_POLICY_PIBT>(win, K, L, tw, obs) : pick_roll(win, K, L, tw, obs);
+using RunRollFn = void (*)(PGeo, PArgs, RArgs, RRun);
+template <Family F>
+using FnOf = std::conditional_t<F == STEP, PartialFn,
+                                std::conditional_t<F == ROLL || F == PIBT_ROLL, RolloutFn, RunRollFn>>;
+
+template <Family F, int WIN, int KF, int LF, int GDE, bool FLAG>
+FnOf<F> inst() {
+  if constexpr (F == STEP) return partial_kernel<WIN, KF, LF, GDE, FLAG>;
+  else if constexpr (F == ROLL) return partial_rollout_kernel<WIN, KF, LF, GDE, FLAG>;
+  else if constexpr (F == PIBT_ROLL) return partial_pibt_rollout_kernel<WIN, KF, LF, GDE, FLAG>;
+  else if constexpr (F == RUN_ROLL) return partial_runner_rollout_kernel<WIN, KF, LF, GDE, FLAG>;
+  else return partial_pibt_runner_rollout_kernel<WIN, KF, LF, GDE, FLAG>;
 }
 
-// partial_runner_rollout_kernel's instances: with the rows the five fast shapes of the
-// runner's step at u8 / int16 tables and the six generic windows (which also take the fast
-// shapes' int32 tables); without the rows one per fast lane group (table width at run time)
-// and one generic.  RULE as above (partial_pibt_runner_rollout_kernel).
-using RunRollFn = void (*)(PGeo, PArgs, RArgs, RRun);
-template <int RULE, int WIN, int KF, int LF, int GDE, bool OBS>
-RunRollFn run_roll_inst() {
-  if constexpr (RULE == MAPFX_POLICY_PIBT) return partial_pibt_runner_rollout_kernel<WIN, KF, LF, GDE, OBS>;
-  else return partial_runner_rollout_kernel<WIN, KF, LF, GDE, OBS>;
-}
-template <int RULE, int WIN, int LF>
-RunRollFn pick_run_roll_fast(int tw) {
-  return tw == 1 ? run_roll_inst<RULE, WIN, 5, LF, 1, true>() : run_roll_inst<RULE, WIN, 5, LF, 2, true>();
-}
-template <int RULE = MAPFX_POLICY_DESCENT>
-RunRollFn pick_run_roll(int win, int K, int L, int tw, bool obs) {
-  if (!obs) {
-    if (L == 8) return run_roll_inst<RULE, 0, 5, 8, 0, false>();
-    if (L == 16) return run_roll_inst<RULE, 0, 5, 16, 0, false>();
-    if (L == 32) return run_roll_inst<RULE, 0, 5, 32, 0, false>();
-    return run_roll_inst<RULE, 0, 0, 0, 0, false>();
-  }
-  if (tw != 0) {
-    if (K == 5 && win == 5 && L == 16) return pick_run_roll_fast<RULE, 5, 16>(tw);
-    if (K == 5 && win == 5 && L == 8) return pick_run_roll_fast<RULE, 5, 8>(tw);
-    if (K == 5 && win == 5 && L == 32) return pick_run_roll_fast<RULE, 5, 32>(tw);
-    if (K == 5 && win == 3 && L == 16) return pick_run_roll_fast<RULE, 3, 16>(tw);
-    if (K == 5 && win == 7 && L == 16) return pick_run_roll_fast<RULE, 7, 16>(tw);
-  }
-  switch (win) {
-    case 0: return run_roll_inst<RULE, 0, 0, 0, 0, true>();
-    case 1: return run_roll_inst<RULE, 1, 0, 0, 0, true>();
-    case 3: return run_roll_inst<RULE, 3, 0, 0, 0, true>();
-    case 5: return run_roll_inst<RULE, 5, 0, 0, 0, true>();
-    case 7: return run_roll_inst<RULE, 7, 0, 0, 0, true>();
-    case 9: return run_roll_inst<RULE, 9, 0, 0, 0, true>();
-  }
+// the fast shape's instance at table width tw (only the GDEs the family offers exist)
+template <Family F, int WIN, int LF, bool FLAG>
+FnOf<F> fast_inst(int tw) {
+  const int gde = FAMILY[F].gde[FLAG][tw];
+  if constexpr (offers(F, FLAG, 0))
+    if (gde == 0) return inst<F, WIN, 5, LF, 0, FLAG>();
+  if constexpr (offers(F, FLAG, 1))
+    if (gde == 1) return inst<F, WIN, 5, LF, 1, FLAG>();
+  if constexpr (offers(F, FLAG, 2))
+    if (gde == 2) return inst<F, WIN, 5, LF, 2, FLAG>();
   return nullptr;
 }
-RunRollFn pick_run_roll_rule(int rule, int win, int K, int L, int tw, bool obs) {
-  return rule == MAPFX_POLICY_PIBT ? pick_run_roll<MAPFX_POLICY_PIBT>(win, K, L, tw, obs)
-                                   : pick_run_roll(win, K, L, tw, obs);
+
+template <Family F, bool FLAG>
+FnOf<F> pick_flag(int win, int K, int L, int tw) {
+  // (a rollout without the rows: any window and K, and a lane group that several pairs name
+  // is the same instance each time)
+  constexpr bool windowed = FLAG || !FAMILY[F].flag_is_obs;
+  if (FAMILY[F].gde[FLAG][tw] != GENERIC) {
+#define X(WIN, LF) \
+  if (L == LF && (!windowed || (K == 5 && win == WIN))) return fast_inst<F, windowed ? WIN : 0, LF, FLAG>(tw);
+    FAST_SHAPES(X)
+#undef X
+  }
+  if constexpr (!windowed) {
+    return inst<F, 0, 0, 0, 0, false>();
+  } else {
+    switch (win) {
+#define X(WIN) \
+  case WIN: return inst<F, WIN, 0, 0, 0, true>();
+      GENERIC_WINDOWS(X)
+#undef X
+    }
+    return nullptr;  // no instance has this window
+  }
+}
+
+// The instance of family F for a configuration's window, K, lane group and table width.
+template <Family F>
+FnOf<F> pick(int win, int K, int L, int tw, bool flag) {
+  return flag ? pick_flag<F, true>(win, K, L, tw) : pick_flag<F, false>(win, K, L, tw);
+}
+
+// every partial_kernel instance: the table walked (mapfx_partial_create raises their
+// dynamic-LDS limit)
+template <typename Fn>
+void each_step_inst(Fn f) {
+#define X(WIN, LF)               \
+  for (int tw = 0; tw < 3; ++tw) \
+    for (int run = 0; run < 2; ++run) f(pick<STEP>(WIN, 5, LF, tw, run != 0));
+  FAST_SHAPES(X)
+#undef X
+#define X(WIN) f(pick<STEP>(WIN, 0, 0, 0, true));
+  GENERIC_WINDOWS(X)
+#undef X
+}
+
+int table_width(const PGeo& g) { return g.gd8 ? 1 : g.gd32 ? 0 : 2; }
+// a handle's rollout instance under policy rule `rule` (MAPFX_POLICY_PIBT has kernels of its own)
+RolloutFn pick_roll(const PGeo& g, int rule, bool obs) {
+  return rule == MAPFX_POLICY_PIBT ? pick<PIBT_ROLL>(g.win, g.K, g.L, table_width(g), obs)
+                                   : pick<ROLL>(g.win, g.K, g.L, table_width(g), obs);
+}
+RunRollFn pick_run_roll(const PGeo& g, int rule, bool obs) {
+  return rule == MAPFX_POLICY_PIBT ? pick<PIBT_RUN_ROLL>(g.win, g.K, g.L, table_width(g), obs)
+                                   : pick<RUN_ROLL>(g.win, g.K, g.L, table_width(g), obs);
+}
+
+// the wave kernels (one wave per env group: N <= 64, sides <= 256), and those with u8 / int16
+// goal tables, which is where the on-device policy and its pibt rule are offered
+bool wave_path(const PGeo& g) { return !g.big; }
+bool wave_path_small_tables(const PGeo& g) { return !g.big && !g.gd32; }
+// the refusal outside wave_path_small_tables(): "<who> needs ..."
+int refuse_small_tables(const char* who) {
+  char msg[256];
+  snprintf(msg, sizeof msg,
+           "%s needs the wave kernel (N <= 64, sides <= 256) and u8 / int16 goal tables (H * W <= 32767)", who);
+  return perr(MAPFX_EINVAL, msg);
+}
+
+// The fast observation path's staging images (one env's rows + 16 bytes of alignment slack
+// each) for a group of 64 lanes (the whole wave) or 32 (each half in turn); the whole wave
+// while the block stays within 40 KB (4 blocks per CU).  `off` is the first free offset; the
+// images alias dep onwards (`alias`) or start at `off`.  Sets off_stage and stage_lanes and
+// returns the new first free offset (`off` when there are no images).
+int place_stage(PGeo& g, int off, bool alias) {
+  g.off_stage = -1;
+  g.stage_lanes = 0;
+  if (g.K == 5 && (g.win == 3 || g.win == 5 || g.win == 7) && g.L >= 8 && g.L <= 32) {
+    for (int G : {64, 32}) {
+      const int st = std::min(g.EPW, G / g.L) * g.stage_env_bytes;
+      const int need = alias ? std::max(off, g.off_dep + st) : off + st;
+      if (need <= (G == 64 ? 40 * 1024 : 64 * 1024)) {
+        g.off_stage = alias ? g.off_dep : off;
+        g.stage_lanes = G;
+        return need;
+      }
+    }
+  }
+  return off;
 }
 
 // The rollout's layout of a wave-kernel configuration: layout()'s regions, with the staging
@@ -2333,19 +2363,11 @@ void layout_rollout(const PGeo& base, bool obs, PGeo& g) {
   g = base;
   int off = g.off_rew + g.EPW * g.rew_env_bytes;
   if (obs && g.off_sqrt >= 0) off = g.off_sqrt + round_up((g.sq_max + 1) * 4, 16);
-  if (!obs) g.off_sqrt = -1;
-  g.off_stage = -1;
-  g.stage_lanes = 0;
-  if (obs && g.K == 5 && (g.win == 3 || g.win == 5 || g.win == 7) && g.L >= 8 && g.L <= 32) {
-    for (int G : {64, 32}) {
-      const int need = off + std::min(g.EPW, G / g.L) * g.stage_env_bytes;
-      if (need <= (G == 64 ? 40 * 1024 : 64 * 1024)) {
-        g.off_stage = off;
-        g.stage_lanes = G;
-        off = need;
-        break;
-      }
-    }
+  if (obs) {
+    off = place_stage(g, off, false);
+  } else {
+    g.off_sqrt = g.off_stage = -1;
+    g.stage_lanes = 0;
   }
   g.lds = round_up(off, 16);
   g.wpb = PARTIAL_MAX_WPB;
@@ -2360,7 +2382,7 @@ int launch(mapfx_partial_t* h, PArgs& a, void* stream) {
   // the runner's fused step, or observation rows to an EpisodeBatch time row
   const bool run = a.ra.act_row != nullptr || a.ra.alive != nullptr || a.obs_rows != nullptr;
   // N > 64 or a side > 256: one workgroup per env, map in HBM
-  const PartialFn fn = g.big ? pick_wg(g.win, wg_apl(g)) : pick(g.win, g.K, g.L, g.gd8 ? 1 : g.gd32 ? 0 : 2, run);
+  const PartialFn fn = g.big ? pick_wg(g.win, wg_apl(g)) : pick<STEP>(g.win, g.K, g.L, table_width(g), run);
   if (!fn) return perr(MAPFX_EINVAL, "obs_window must be one of 0, 1, 3, 5, 7, 9");
   if (g.big)
     return launch_kernel(fn, dim3(g.E), dim3(WG_THREADS), g.wg_lds, (hipStream_t)stream, nullptr, nullptr,
@@ -2398,6 +2420,92 @@ void fill_out(PArgs& a, const mapfx_partial_out* o) {
   a.state = o->state;
   a.avail = o->avail;
   a.err = o->err;
+}
+
+// Where every entry point that launches the env kernels starts: the handle and the state
+// checked, `a` cleared and filled from the state and the outputs (out may be NULL).
+int begin(const mapfx_partial_t* h, const mapfx_partial_state* st, const mapfx_partial_out* out, PArgs& a) {
+  if (!h) return perr(MAPFX_EINVAL, "NULL handle");
+  if (int rc = check_state(h, st)) return rc;
+  memset(&a, 0, sizeof(a));
+  fill_state(a, st);
+  fill_out(a, out);
+  return MAPFX_OK;
+}
+
+// The one step: mapfx_partial_step, and with `ra` the runner's fused step.  obs_rows not
+// NULL: the observation rows go to an EpisodeBatch time row (obs_rows + e * obs_env_stride
+// floats, envs with obs_mask[e] != 0) instead of out->obs.
+int step(mapfx_partial_t* h, const mapfx_partial_state* st, const void* actions, int action_dtype,
+         const mapfx_runner_acts* ra, const mapfx_partial_out* out, float* obs_rows, long long obs_env_stride,
+         const uint8_t* obs_mask, void* stream) {
+  PArgs a;
+  if (int rc = begin(h, st, out, a)) return rc;
+  if (!actions || (ra && !ra->act_row))
+    return perr(MAPFX_EINVAL, ra ? "NULL actions / rows map" : "NULL actions");
+  if (action_dtype < MAPFX_I8 || action_dtype > MAPFX_I64) return perr(MAPFX_EINVAL, "bad action_dtype");
+  if (obs_rows) {
+    a.obs = nullptr;
+    a.obs_rows = obs_rows;
+    a.obs_env_stride = obs_env_stride;
+    a.obs_mask = obs_mask;
+  }
+  a.actions = actions;
+  a.act_dtype = action_dtype;
+  if (ra) a.ra = *ra;
+  a.do_step = 1;
+  return launch(h, a, stream);
+}
+
+// ---- what the two fused rollouts (mapfx_partial_rollout's wave path, mapfx_partial_rollout_runner)
+// share; `who` is the public call their messages name ----
+// actions or a policy, and the policy only where it is offered
+int check_policy(const mapfx_partial_t* h, const char* who, const void* actions, const mapfx_partial_policy* pol) {
+  char msg[96];
+  if (!actions && !pol) {
+    snprintf(msg, sizeof msg, "%s: actions or a policy is required", who);
+    return perr(MAPFX_EINVAL, msg);
+  }
+  if (actions || wave_path_small_tables(h->geo)) return MAPFX_OK;
+  snprintf(msg, sizeof msg, "%s: the on-device policy", who);
+  return refuse_small_tables(msg);
+}
+
+// the wave launch's arguments on top of begin()'s `a`; without actions the policy `pol` acts
+void fused_args(const mapfx_partial_t* h, const mapfx_partial_state* st, int32_t T, const void* actions,
+                int action_dtype, const mapfx_partial_policy* pol, PArgs& a, RArgs& ro) {
+  const bool policy = actions == nullptr;
+  a.bonus_lut = h->bonus_lut;
+  if (h->no_nbcarry) a.pnbr = nullptr;
+  // policy mode: the prologue's unconditional action load reads the positions instead
+  a.actions = policy ? (const void*)st->pos : actions;
+  a.act_dtype = policy ? MAPFX_I8 : action_dtype;
+  a.do_step = 1;
+  memset(&ro, 0, sizeof(ro));
+  ro.T = T;
+  ro.policy = policy ? 1 : 0;
+  if (policy) {
+    ro.t0 = pol->t0;
+    ro.seed = pol->seed;
+    ro.eps_q = pol->eps_q;
+  }
+  ro.env_offset = (long long)h->cfg.env_offset;
+}
+
+// the launch of instance `fn` over the rollout's layout with or without the rows (`more`:
+// the family's arguments after PGeo and PArgs)
+template <typename... P, typename... A>
+int launch_fused(const mapfx_partial_t* h, void (*fn)(P...), bool obs, void* stream, const char* what,
+                 const PArgs& a, const A&... more) {
+  if (!fn) return perr(MAPFX_EINVAL, "obs_window must be one of 0, 1, 3, 5, 7, 9");
+  const PGeo& gr = h->geo_roll[obs ? 1 : 0];
+  const int waves = (h->geo.E + gr.EPW - 1) / gr.EPW;
+  return launch_kernel(fn, dim3((waves + gr.wpb - 1) / gr.wpb), dim3(64 * gr.wpb), gr.lds * gr.wpb,
+                       (hipStream_t)stream, nullptr, nullptr, what, NOTED, gr, a, more...);
+}
+
+int raise_lds(const void* fn, int bytes, const char* what) {
+  return check_hip(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes), what);
 }
 
 // the goal-distance BFS instance `fn` (tables of DT), recorded for mapfx_last_kernel
@@ -2485,25 +2593,8 @@ const char* layout(const mapfx_partial_cfg& c, PGeo& g) {
     g.off_sqrt = off;
     off += round_up((g.sq_max + 1) * 4, 16);
   }
-  // the fast observation path's staging images (one env's rows + 16 bytes of alignment
-  // slack each) for a group of 64 lanes (the whole wave) or 32 (each half in turn),
-  // aliasing dep onwards; the whole wave while the block stays within 40 KB (4 blocks
-  // per CU)
-  g.off_stage = -1;
-  g.stage_lanes = 0;
   g.stage_env_bytes = round_up(L * g.D * 4 + 16, 16);
-  if (g.K == 5 && (g.win == 3 || g.win == 5 || g.win == 7) && L >= 8 && L <= 32) {
-    for (int G : {64, 32}) {
-      const int st = std::min(EPW, G / L) * g.stage_env_bytes;
-      const int need = std::max(off, g.off_dep + st);
-      if (need <= (G == 64 ? 40 * 1024 : 64 * 1024)) {
-        g.off_stage = g.off_dep;
-        g.stage_lanes = G;
-        off = need;
-        break;
-      }
-    }
-  }
+  off = place_stage(g, off, true);  // (the step's images alias dep onwards)
   g.lds = round_up(off, 16);
   // waves per block: up to PARTIAL_MAX_WPB while the block's LDS fits the CU
   g.wpb = 1;
@@ -2568,9 +2659,7 @@ int mapfx_partial_create(const mapfx_partial_cfg* cfg, mapfx_partial_t** out) {
   int rc = MAPFX_OK;
   if (g.big) {
     if (g.wg_lds > 64 * 1024)
-      rc = check_hip(hipFuncSetAttribute((const void*)pick_wg(g.win, wg_apl(g)),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, g.wg_lds),
-                     "hipFuncSetAttribute(partial_wg_kernel LDS)");
+      rc = raise_lds((const void*)pick_wg(g.win, wg_apl(g)), g.wg_lds, "hipFuncSetAttribute(partial_wg_kernel LDS)");
     if (!rc && g.huge_lds > 64 * 1024 &&
         hipFuncSetAttribute(huge_bfs, hipFuncAttributeMaxDynamicSharedMemorySize, g.huge_lds) != hipSuccess) {
       (void)hipGetLastError();
@@ -2581,14 +2670,9 @@ int mapfx_partial_create(const mapfx_partial_cfg* cfg, mapfx_partial_t** out) {
       rc = perr(MAPFX_EINVAL, msg);
     }
   } else if (g.lds * g.wpb > 64 * 1024) {
-    for (int win : PICK_WIN)  // every instance pick() can return
-      for (int K : PICK_K)
-        for (int L : PICK_L)
-          for (int tw : PICK_TW)
-            for (int run = 0; run < 2 && !rc; ++run)
-              rc = check_hip(hipFuncSetAttribute((const void*)pick(win, K, L, tw, run != 0),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, g.lds * g.wpb),
-                             "hipFuncSetAttribute(partial_kernel LDS)");
+    each_step_inst([&](PartialFn fn) {
+      if (!rc) rc = raise_lds((const void*)fn, g.lds * g.wpb, "hipFuncSetAttribute(partial_kernel LDS)");
+    });
   }
   if (!g.big) {  // the rollout's two layouts and this configuration's two instances
     for (int i = 0; i < 4 && !rc; ++i) {  // (i >> 1: the policy rule, pibt where it is offered)
@@ -2596,16 +2680,12 @@ int mapfx_partial_create(const mapfx_partial_cfg* cfg, mapfx_partial_t** out) {
       if (rule != MAPFX_POLICY_DESCENT && g.gd32) break;
       PGeo& gr = h->geo_roll[obs];
       if (rule == MAPFX_POLICY_DESCENT) layout_rollout(g, obs != 0, gr);
-      const RolloutFn fn = pick_roll_rule(rule, g.win, g.K, g.L, g.gd8 ? 1 : g.gd32 ? 0 : 2, obs != 0);
-      if (fn && gr.lds * gr.wpb > 64 * 1024)
-        rc = check_hip(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           gr.lds * gr.wpb),
-                       "hipFuncSetAttribute(partial_rollout_kernel LDS)");
-      const RunRollFn rfn = pick_run_roll_rule(rule, g.win, g.K, g.L, g.gd8 ? 1 : g.gd32 ? 0 : 2, obs != 0);
-      if (!rc && rfn && gr.lds * gr.wpb > 64 * 1024)
-        rc = check_hip(hipFuncSetAttribute((const void*)rfn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           gr.lds * gr.wpb),
-                       "hipFuncSetAttribute(partial_runner_rollout_kernel LDS)");
+      if (gr.lds * gr.wpb <= 64 * 1024) continue;
+      const RolloutFn fn = pick_roll(g, rule, obs != 0);
+      if (fn) rc = raise_lds((const void*)fn, gr.lds * gr.wpb, "hipFuncSetAttribute(partial_rollout_kernel LDS)");
+      const RunRollFn rfn = pick_run_roll(g, rule, obs != 0);
+      if (!rc && rfn)
+        rc = raise_lds((const void*)rfn, gr.lds * gr.wpb, "hipFuncSetAttribute(partial_runner_rollout_kernel LDS)");
     }
   }
   if (rc) return rc;
@@ -2714,13 +2794,8 @@ int mapfx_partial_draw(mapfx_partial_t* h, const mapfx_partial_scen* sc, void* s
 
 int mapfx_partial_reset(mapfx_partial_t* h, const mapfx_partial_state* st, const uint8_t* env_mask,
                         const mapfx_partial_out* out, void* stream) {
-  if (!h) return perr(MAPFX_EINVAL, "NULL handle");
-  int rc = check_state(h, st);
-  if (rc) return rc;
   PArgs a;
-  memset(&a, 0, sizeof(a));
-  fill_state(a, st);
-  fill_out(a, out);
+  if (int rc = begin(h, st, out, a)) return rc;
   a.reward = nullptr;
   a.do_reset = 1;
   a.reset_mask = env_mask;
@@ -2729,88 +2804,29 @@ int mapfx_partial_reset(mapfx_partial_t* h, const mapfx_partial_state* st, const
 
 int mapfx_partial_step(mapfx_partial_t* h, const mapfx_partial_state* st, const void* actions,
                        int action_dtype, const mapfx_partial_out* out, void* stream) {
-  if (!h) return perr(MAPFX_EINVAL, "NULL handle");
-  int rc = check_state(h, st);
-  if (rc) return rc;
-  if (!actions) return perr(MAPFX_EINVAL, "NULL actions");
-  if (action_dtype < MAPFX_I8 || action_dtype > MAPFX_I64) return perr(MAPFX_EINVAL, "bad action_dtype");
-  PArgs a;
-  memset(&a, 0, sizeof(a));
-  fill_state(a, st);
-  fill_out(a, out);
-  a.actions = actions;
-  a.act_dtype = action_dtype;
-  a.do_step = 1;
-  return launch(h, a, stream);
+  return step(h, st, actions, action_dtype, nullptr, out, nullptr, 0, nullptr, stream);
 }
 
-// mapfx_partial_step with the observation rows written to an EpisodeBatch time row
-// (obs_rows + e * obs_env_stride floats, envs with obs_mask[e] != 0) instead of
-// out->obs: the runner's fused step (runner.hip), internal.h
-int mapfx_partial_step_rows(mapfx_partial_t* h, const mapfx_partial_state* st, const void* actions,
-                            int action_dtype, const mapfx_partial_out* out, float* obs_rows,
-                            long long obs_env_stride, const uint8_t* obs_mask, void* stream) {
-  if (!h) return perr(MAPFX_EINVAL, "NULL handle");
-  int rc = check_state(h, st);
-  if (rc) return rc;
-  if (!actions) return perr(MAPFX_EINVAL, "NULL actions");
-  if (action_dtype < MAPFX_I8 || action_dtype > MAPFX_I64) return perr(MAPFX_EINVAL, "bad action_dtype");
-  PArgs a;
-  memset(&a, 0, sizeof(a));
-  fill_state(a, st);
-  fill_out(a, out);
-  a.obs = nullptr;
-  a.obs_rows = obs_rows;
-  a.obs_env_stride = obs_env_stride;
-  a.obs_mask = obs_mask;
-  a.actions = actions;
-  a.act_dtype = action_dtype;
-  a.do_step = 1;
-  return launch(h, a, stream);
-}
+int mapfx_partial_fuses_post(const mapfx_partial_t* h) { return h && wave_path(h->geo) ? 1 : 0; }
 
-int mapfx_partial_fuses_post(const mapfx_partial_t* h) { return h && !h->geo.big ? 1 : 0; }
-
+// the runner's fused step (runner.hip), internal.h
 int mapfx_partial_step_runner(mapfx_partial_t* h, const mapfx_partial_state* st, const void* actions,
                               int action_dtype, const mapfx_runner_acts* ra, const mapfx_partial_out* out,
                               float* obs_rows, long long obs_env_stride, const uint8_t* obs_mask,
                               void* stream) {
-  if (!h) return perr(MAPFX_EINVAL, "NULL handle");
-  int rc = check_state(h, st);
-  if (rc) return rc;
-  if (!actions || !ra || !ra->act_row) return perr(MAPFX_EINVAL, "NULL actions / rows map");
-  if (action_dtype < MAPFX_I8 || action_dtype > MAPFX_I64) return perr(MAPFX_EINVAL, "bad action_dtype");
-  PArgs a;
-  memset(&a, 0, sizeof(a));
-  fill_state(a, st);
-  fill_out(a, out);
-  if (obs_rows) {
-    a.obs = nullptr;
-    a.obs_rows = obs_rows;
-    a.obs_env_stride = obs_env_stride;
-    a.obs_mask = obs_mask;
-  }
-  a.actions = actions;
-  a.act_dtype = action_dtype;
-  a.ra = *ra;
-  a.do_step = 1;
-  return launch(h, a, stream);
+  static const mapfx_runner_acts no_rows_map = {};  // (ra NULL is refused like its act_row NULL)
+  return step(h, st, actions, action_dtype, ra ? ra : &no_rows_map, out, obs_rows, obs_env_stride, obs_mask, stream);
 }
 
 int mapfx_partial_observe(mapfx_partial_t* h, const mapfx_partial_state* st,
                           const mapfx_partial_out* out, void* stream) {
-  if (!h) return perr(MAPFX_EINVAL, "NULL handle");
-  int rc = check_state(h, st);
-  if (rc) return rc;
   PArgs a;
-  memset(&a, 0, sizeof(a));
-  fill_state(a, st);
-  fill_out(a, out);
+  if (int rc = begin(h, st, out, a)) return rc;
   a.reward = nullptr;
   return launch(h, a, stream);
 }
 
-int mapfx_partial_rollout_fused(const mapfx_partial_t* h) { return h && !h->geo.big ? 1 : 0; }
+int mapfx_partial_rollout_fused(const mapfx_partial_t* h) { return h && wave_path(h->geo) ? 1 : 0; }
 
 // internal.h: what repair.hip needs of a handle
 int mapfx_partial_shape_of(const mapfx_partial_t* h, mapfx_partial_shape* s) {
@@ -2824,25 +2840,17 @@ int mapfx_partial_check_state(const mapfx_partial_t* h, const mapfx_partial_stat
 int mapfx_partial_rollout(mapfx_partial_t* h, const mapfx_partial_state* st, int32_t T, const void* actions,
                           int action_dtype, const mapfx_partial_policy* pol, int32_t autoreset,
                           const mapfx_partial_traj* traj, void* stream) {
-  if (!h) return perr(MAPFX_EINVAL, "NULL handle");
-  int rc = check_state(h, st);
+  PArgs a;
+  int rc = begin(h, st, nullptr, a);
   if (rc) return rc;
   if (T < 1 || T > 65536) return perr(MAPFX_EINVAL, "mapfx_partial_rollout: T must be in 1..65536");
   if (action_dtype < MAPFX_I8 || action_dtype > MAPFX_I64) return perr(MAPFX_EINVAL, "bad action_dtype");
-  if (!actions && !pol) return perr(MAPFX_EINVAL, "mapfx_partial_rollout: actions or a policy is required");
+  if ((rc = check_policy(h, "mapfx_partial_rollout", actions, pol))) return rc;
   const PGeo& g = h->geo;
-  const bool policy = actions == nullptr;
-  if (policy && (g.big || g.gd32))
-    return perr(MAPFX_EINVAL,
-                "mapfx_partial_rollout: the on-device policy needs the wave kernel (N <= 64, sides <= 256) "
-                "and u8 / int16 goal tables (H * W <= 32767)");
   if (g.E == 0) return MAPFX_OK;
   const mapfx_partial_traj none = {};
   const mapfx_partial_traj& tj = traj ? *traj : none;
   const long long EN = (long long)g.E * g.N;
-  PArgs a;
-  memset(&a, 0, sizeof(a));
-  fill_state(a, st);
   a.act_dtype = action_dtype;
   a.do_step = 1;
   a.err = tj.err;
@@ -2878,37 +2886,19 @@ int mapfx_partial_rollout(mapfx_partial_t* h, const mapfx_partial_state* st, int
     }
     return rc;
   }
-  const bool obs = tj.obs != nullptr;
-  const RolloutFn fn = pick_roll_rule(policy ? h->rule : MAPFX_POLICY_DESCENT, g.win, g.K, g.L,
-                                      g.gd8 ? 1 : g.gd32 ? 0 : 2, obs);
-  if (!fn) return perr(MAPFX_EINVAL, "obs_window must be one of 0, 1, 3, 5, 7, 9");
-  a.bonus_lut = h->bonus_lut;
-  if (h->no_nbcarry) a.pnbr = nullptr;
-  // policy mode: the prologue's unconditional action load reads the positions instead
-  a.actions = policy ? (const void*)st->pos : actions;
-  if (policy) a.act_dtype = MAPFX_I8;
+  RArgs ro;
+  fused_args(h, st, T, actions, action_dtype, pol, a, ro);
   a.reward = tj.reward;
   a.obs = tj.obs;
   a.state = tj.state;
   a.avail = tj.avail;
-  RArgs ro;
-  memset(&ro, 0, sizeof(ro));
-  ro.T = T;
   ro.autoreset = autoreset ? 1 : 0;
-  ro.policy = policy ? 1 : 0;
-  if (policy) {
-    ro.t0 = pol->t0;
-    ro.seed = pol->seed;
-    ro.eps_q = pol->eps_q;
-    ro.actions = tj.actions;
-  }
-  ro.env_offset = (long long)h->cfg.env_offset;
+  if (ro.policy) ro.actions = tj.actions;
   ro.pos = tj.pos;
   ro.terminated = tj.terminated;
-  const PGeo& gr = h->geo_roll[obs ? 1 : 0];
-  const int waves = (g.E + gr.EPW - 1) / gr.EPW;
-  return launch_kernel(fn, dim3((waves + gr.wpb - 1) / gr.wpb), dim3(64 * gr.wpb), gr.lds * gr.wpb,
-                       (hipStream_t)stream, nullptr, nullptr, "partial_rollout_kernel launch", NOTED, gr, a, ro);
+  const bool obs = tj.obs != nullptr;
+  return launch_fused(h, pick_roll(g, ro.policy ? h->rule : MAPFX_POLICY_DESCENT, obs), obs, stream,
+                      "partial_rollout_kernel launch", a, ro);
 }
 
 int mapfx_partial_bind_err(mapfx_partial_t* h, int32_t* err) {
@@ -2920,7 +2910,7 @@ int mapfx_partial_bind_err(mapfx_partial_t* h, int32_t* err) {
 int mapfx_partial_policy_rule_offered(const mapfx_partial_t* h, int32_t rule) {
   if (!h) return 0;
   if (rule == MAPFX_POLICY_DESCENT) return 1;
-  return rule == MAPFX_POLICY_PIBT && !h->geo.big && !h->geo.gd32 ? 1 : 0;
+  return rule == MAPFX_POLICY_PIBT && wave_path_small_tables(h->geo) ? 1 : 0;
 }
 
 int mapfx_partial_policy_rule(mapfx_partial_t* h, int32_t rule) {
@@ -2928,15 +2918,13 @@ int mapfx_partial_policy_rule(mapfx_partial_t* h, int32_t rule) {
   if (rule != MAPFX_POLICY_DESCENT && rule != MAPFX_POLICY_PIBT)
     return perr(MAPFX_EINVAL, "mapfx_partial_policy_rule: unknown rule");
   if (!mapfx_partial_policy_rule_offered(h, rule))
-    return perr(MAPFX_EINVAL,
-                "mapfx_partial_policy_rule: MAPFX_POLICY_PIBT needs the wave kernel (N <= 64, sides <= 256) "
-                "and u8 / int16 goal tables (H * W <= 32767)");
+    return refuse_small_tables("mapfx_partial_policy_rule: MAPFX_POLICY_PIBT");
   h->rule = rule;
   return MAPFX_OK;
 }
 
 int mapfx_partial_runner_rollout_offered(const mapfx_partial_t* h, int policy) {
-  return h && !h->geo.big && !(policy && h->geo.gd32) ? 1 : 0;
+  return h && (policy ? wave_path_small_tables(h->geo) : wave_path(h->geo)) ? 1 : 0;
 }
 
 // The fused launch of mapfx_runner_rollout (runner.hip, which checks the runner's half of
@@ -2944,49 +2932,27 @@ int mapfx_partial_runner_rollout_offered(const mapfx_partial_t* h, int policy) {
 int mapfx_partial_rollout_runner(mapfx_partial_t* h, const mapfx_partial_state* st, int32_t T, const void* actions,
                                  int action_dtype, const mapfx_partial_policy* pol, const mapfx_runner_acts* ra,
                                  const mapfx_runner_roll* rr, void* stream) {
-  if (!h) return perr(MAPFX_EINVAL, "NULL handle");
-  int rc = check_state(h, st);
+  PArgs a;
+  int rc = begin(h, st, nullptr, a);
   if (rc) return rc;
   if (!ra || !rr || !ra->alive || !ra->alive_prev) return perr(MAPFX_EINVAL, "mapfx_runner_rollout: NULL runner rows");
   if (T < 1) return perr(MAPFX_EINVAL, "mapfx_runner_rollout: T must be >= 1");
-  if (!actions && !pol) return perr(MAPFX_EINVAL, "mapfx_runner_rollout: actions or a policy is required");
-  const bool policy = actions == nullptr;
-  if (!policy && (action_dtype < MAPFX_I8 || action_dtype > MAPFX_I64)) return perr(MAPFX_EINVAL, "bad action_dtype");
+  // (check_policy refuses only without actions, the two checks after it only with them)
+  if ((rc = check_policy(h, "mapfx_runner_rollout", actions, pol))) return rc;
+  if (actions && (action_dtype < MAPFX_I8 || action_dtype > MAPFX_I64)) return perr(MAPFX_EINVAL, "bad action_dtype");
   const PGeo& g = h->geo;
-  if (!mapfx_partial_runner_rollout_offered(h, policy ? 1 : 0))
-    return perr(MAPFX_EINVAL,
-                policy ? "mapfx_runner_rollout: the on-device policy needs the wave kernel (N <= 64, sides <= 256) "
-                         "and u8 / int16 goal tables (H * W <= 32767)"
-                       : "mapfx_runner_rollout: offered on the wave kernel only (N <= 64, sides <= 256)");
+  if (!wave_path(g))
+    return perr(MAPFX_EINVAL, "mapfx_runner_rollout: offered on the wave kernel only (N <= 64, sides <= 256)");
   if (g.E == 0) return MAPFX_OK;
-  const bool obs = rr->obs_rows != nullptr;
-  const RunRollFn fn = pick_run_roll_rule(policy ? h->rule : MAPFX_POLICY_DESCENT, g.win, g.K, g.L,
-                                          g.gd8 ? 1 : g.gd32 ? 0 : 2, obs);
-  if (!fn) return perr(MAPFX_EINVAL, "obs_window must be one of 0, 1, 3, 5, 7, 9");
-  PArgs a;
-  memset(&a, 0, sizeof(a));
-  fill_state(a, st);
-  a.bonus_lut = h->bonus_lut;
-  if (h->no_nbcarry) a.pnbr = nullptr;
-  a.actions = policy ? (const void*)st->pos : actions;  // (policy: the prologue's dummy load)
-  a.act_dtype = policy ? MAPFX_I8 : action_dtype;
-  a.do_step = 1;
+  RArgs ro;
+  fused_args(h, st, T, actions, action_dtype, pol, a, ro);
   a.err = h->err;
   a.obs_rows = rr->obs_rows;
   a.obs_env_stride = rr->obs_sb;
   a.ra = *ra;
   a.ra.act_row = nullptr;
   a.ra.cmp_bs = nullptr;
-  RArgs ro;
-  memset(&ro, 0, sizeof(ro));
-  ro.T = T;
-  ro.policy = policy ? 1 : 0;
-  if (policy) {
-    ro.t0 = pol->t0 + ra->ts;  // the counter is the absolute row pol->t0 + ts
-    ro.seed = pol->seed;
-    ro.eps_q = pol->eps_q;
-  }
-  ro.env_offset = (long long)h->cfg.env_offset;
+  if (ro.policy) ro.t0 += ra->ts;  // the counter is the absolute row pol->t0 + ts
   RRun rn;
   memset(&rn, 0, sizeof(rn));
   rn.ts0 = ra->ts;
@@ -2996,11 +2962,9 @@ int mapfx_partial_rollout_runner(mapfx_partial_t* h, const mapfx_partial_state* 
   rn.avail_st = rr->avail_st;
   rn.filled_st = rr->filled_st;
   rn.stale_out = rr->stale_out;
-  const PGeo& gr = h->geo_roll[obs ? 1 : 0];
-  const int waves = (g.E + gr.EPW - 1) / gr.EPW;
-  return launch_kernel(fn, dim3((waves + gr.wpb - 1) / gr.wpb), dim3(64 * gr.wpb), gr.lds * gr.wpb,
-                       (hipStream_t)stream, nullptr, nullptr, "partial_runner_rollout_kernel launch", NOTED, gr, a,
-                       ro, rn);
+  const bool obs = rr->obs_rows != nullptr;
+  return launch_fused(h, pick_run_roll(g, ro.policy ? h->rule : MAPFX_POLICY_DESCENT, obs), obs, stream,
+                      "partial_runner_rollout_kernel launch", a, ro, rn);
 }
 
 }  // extern "C"
